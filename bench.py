@@ -7,11 +7,15 @@ HBM when the timed region starts.  One process per GPU; for N > 1 launch with to
 rank owns its own shard of reads (weak scaling, no data-path collective) and the additive counter
 buffer is all-reduced over RCCL once at the end of the timed region.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant kernel,
-HIP-event timed inside the timed region), `cpu_baseline` (the oracle on the host cores, on a
-bounded sample of the same workload, outside the timed region), `parity_sample` (the records the
-timed step left behind and the counters of the same reads against that oracle run) and `e2e`
-(bin/fastplong_amd on the same reads as FASTQ text: /dev/null, one file, 16 --split files).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the driver's contract fields,
+the workload's description and `counters_check` (the counters of the timed steps add up to steps x reads).
+--dump-outputs DIR also writes what the last timed step computed as .npy files (dump_outputs()).
+
+--full adds everything else, outside the timed region: `roofline` (dominant kernel, HIP-event timed inside the
+timed region, plus three steps in line behind it), `cpu_baseline` (the oracle on the host cores, on a bounded sample
+of the same workload), `parity_sample` (the records the timed step left behind and the counters of the same reads
+against that oracle run) and `e2e` (bin/fastplong_amd on the same reads as FASTQ text: /dev/null, one file, 16 --split
+files).
 """
 import argparse
 import json
@@ -35,6 +39,12 @@ LINE_LIMIT = 4096  # bytes of the stdout line: the driver keeps the last 8 KB of
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 ALGO_BYTES_PER_BASE = 2.0  # one seq byte + one quality byte, each read once
+
+# --dump-outputs: at most this many bytes in all; larger outputs are dumped as a fixed, seeded sample
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_READS = 1 << 17  # records of this many reads at most
+DUMP_COUNTERS = 1 << 21  # entries of the counter buffer at most
+DUMP_SEED = 20251015
 
 WORKLOADS = {
     # BASELINE.json configs[2]: the metric's "trim+cut+filter" pipeline on the configs[1] reads
@@ -636,8 +646,48 @@ def compact_line(out):
     return c
 
 
+def _sample(n, k, seed):
+    """indices 0..n-1 when n <= k, else k of them drawn without replacement by a generator seeded with `seed`, sorted"""
+    import numpy as np
+
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, res_t, n_reads, counters, steps):
+    """What the timed path hands its caller after its last step, as float64 arrays `out_dir/<name>.npy` (every value is an
+    integer below 2**53, so float64 holds it exactly):
+      records_<field>      one per field of struct fpl_read_result (the reserved bytes left out), for the reads listed in
+      records_read_index   -- every read of the batch, or a fixed, seeded sample of DUMP_READS reads of a larger one;
+      counters             the counter buffer of ONE step: the timed steps' sum / steps (every counter is additive and every
+                           step processes the same batch), at the entries listed in
+      counters_index       -- every entry, or a fixed, seeded sample of DUMP_COUNTERS entries of a larger buffer.
+    The batch is generated from fixed seeds, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+
+    from fastplong_amd import abi
+
+    rec = np.ascontiguousarray(res_t.cpu().numpy()).view(abi.RESULT_DTYPE)[:n_reads]
+    ridx = _sample(n_reads, DUMP_READS, DUMP_SEED)
+    arrays = {"records_read_index": ridx}
+    for name in rec.dtype.names:
+        if name != "reserved":
+            arrays["records_" + name] = rec[name][ridx]
+    cidx = _sample(len(counters), DUMP_COUNTERS, DUMP_SEED + 1)
+    arrays["counters_index"] = cidx
+    arrays["counters"] = counters[cidx].astype(np.float64) / steps
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def emit(out, full_path):
-    """the full object -> `full_path` and stderr; its compact form -> ONE stdout line of at most LINE_LIMIT bytes"""
+    """the full object -> `full_path` (when given) and stderr; its compact form -> ONE stdout line of at most LINE_LIMIT bytes"""
     full = json.dumps(out)
     if full_path:
         try:
@@ -700,27 +750,36 @@ def main(argv=None, rig=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (0 = the workload's own: 1 M for c2/c3, 2.5 M for c4, 0.5 M for c5)")
     ap.add_argument("--median-len", type=int, default=0, help="ablation only: median read length of the ONT-like workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, outside the timed region: the roofline object "
+                         "(HIP events around every kernel of the timed steps, three more steps in line), the oracle's check of the "
+                         "timed batch, the CPU baseline and the end-to-end legs; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (records, counters of one step) to DIR/<name>.npy")
     ap.add_argument("--e2e-reads", type=int, default=1_000_000,
-                    help="reads of rank 0's batch written as FASTQ (once per GPU) and run through ONE bin/fastplong_amd --gpus N (0 = skip)")
+                    help="--full: reads of rank 0's batch written as FASTQ (once per GPU) and run through ONE bin/fastplong_amd --gpus N (0 = skip)")
     ap.add_argument("--e2e-copies", type=int, default=4,
                     help="N = 1: a second end-to-end run over this many copies of the reads, so that the process's fixed cost "
                          "(HIP context, reports, exit) weighs less (0 or 1 = skip)")
     ap.add_argument("--parity-reads", type=int, default=200_000,
-                    help="outside the timed region: the first reads of the timed batch (at N = 1 at least the CPU baseline's sample) whose "
+                    help="--full: the first reads of the timed batch (at N = 1 at least the CPU baseline's sample) whose "
                          "records and counters are checked against the oracle (0 = skip)")
     ap.add_argument("--parity-strided", type=int, default=2000,
                     help="... and this many reads spread evenly over the rest of the timed batch (records only)")
     ap.add_argument("--workload", default="c3_full_pipeline", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-bases", type=float, default=6e9, help="size of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-bases", type=float, default=6e9, help="--full: size of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--set", default="", help="ablation only: comma separated fpl_options overrides, e.g. adapter_enabled=0")
     ap.add_argument("--e2e-full", action="store_true",
-                    help="also run the long end-to-end legs: gzip in / out, the large input (--e2e-copies) with --chunk_mb and the "
-                         "null-device host-ceiling runs (minutes; the default run keeps to /dev/null, one file, --split on --e2e-reads)")
-    ap.add_argument("--full-json", default=os.path.join("gpurun_out", "bench_full.json"),
-                    help="where the FULL result object goes (the stdout line is its compact form, a few KB)")
+                    help="implies --full; also run the long end-to-end legs: gzip in / out, the large input (--e2e-copies) with --chunk_mb "
+                         "and the null-device host-ceiling runs (minutes; --full alone keeps to /dev/null, one file, --split on --e2e-reads)")
+    ap.add_argument("--full-json", default=None,
+                    help="also write the FULL result object to this file (it goes to stderr in any case; the stdout line is its "
+                         "compact form, a few KB)")
     ap.add_argument("--hbm-traffic", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run")
     args = ap.parse_args(argv)
+    if args.e2e_full:
+        args.full = True
 
     import numpy as np
     import torch
@@ -775,7 +834,9 @@ def main(argv=None, rig=None):
         step()
     rig.synchronize(dev)
     eng.reset_counters()
-    eng.enable_timing(True)  # HIP events around every kernel, on the launch stream, inside the timed region
+    # HIP events around every kernel, on the launch stream, inside the timed region -- in a plain run as well: the timed steps
+    # are the same with or without --full (without the events the same steps measured 745 Gbases/s against 786 on c3)
+    eng.enable_timing(True)
     if world > 1:
         dist.barrier()
     rig.synchronize(dev)
@@ -796,8 +857,56 @@ def main(argv=None, rig=None):
         dist.all_reduce(tb, op=dist.ReduceOp.SUM)
     dt = float(tt.item())
     total_bases = int(tb.item())
-    ktimes, nbatches = eng.kernel_times()
     counters_timed = eng.counters() if rank == 0 else None  # (the counters of the timed steps: the pass below adds to them)
+    if args.dump_outputs and rank == 0:  # (before anything else runs on the batch: res_t holds the last timed step's records)
+        dump_outputs(args.dump_outputs, res_t, n, counters_timed, args.steps)
+    ms_per_step = dt / args.steps * 1e3
+    adapters = (ad_start, ad_end, ad_fasta)
+    out = None
+    if rank == 0:
+        v = abi.CountersView(counters_timed, C, eng.n_adapters)
+        reads_ok = int(v.pre.reads) == args.steps * n * (world if world > 1 else 1) and \
+            int(v.pre.length_sum) == args.steps * total_bases
+        out = {
+            "metric": "Gbases/s processed (trim+cut+filter)",
+            "value": total_bases * args.steps / dt / 1e9,
+            "unit": "Gbases/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "config": {
+                "workload": "%s%s: BASELINE.json configs[%d] -- %d synthetic reads per GPU, %s, %s; inputs resident in HBM" % (
+                    args.workload, (" [ABLATION " + " ".join(filter(None, [args.set, args.median_len and "median-len=%d" % args.median_len])) + "]")
+                    if (args.set or args.median_len) else "", wl["config"], n, wl["reads_desc"], wl["flags"]),
+                "reads_per_gpu": n, "bases_per_gpu": n_bases, "max_read_len": max_len,
+                "parallelism": "shard%d (independent read shards, one RCCL all-reduce of the counters)" % world,
+                "pipelining": ("the steps are enqueued back to back on one stream; the end trims of step k + 1 run on a stream of their own beside "
+                               "k_scan of step k, two of their blocks per CU (fpl_assume_inputs_ready: the batch is resident), so "
+                               "kernel_ms.k_trim_ends is what is LEFT of them in line and kernel_ms.k_scan is k_scan WITH the trims beside it -- "
+                               "roofline.kernel_ms_alone / frac_alone: the same kernel with nothing beside it") if trim_ahead else "none: every kernel of a step in line",
+            },
+            "counters_check": {"reads_in": int(v.pre.reads), "bases_in": int(v.pre.length_sum),
+                               "fragments_out": int(v.post.reads), "bases_out": int(v.post.length_sum),
+                               "expected_reads_in": args.steps * n * world if world > 1 else args.steps * n,
+                               "expected_bases_in": args.steps * total_bases, "ok": bool(reads_ok)},
+        }
+    if not args.full:
+        eng.close()
+        if rank == 0:
+            emit(out, args.full_json)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below runs outside the timed region and adds to the line
+    ktimes, nbatches = eng.kernel_times()
     # With the end trims ahead of the main stream, the k_trim_ends stage of the timed region is what is LEFT of them in line, not a
     # kernel duration.  Three more steps with every kernel in line (promise withdrawn), outside the timed region, give the stage
     # times the roofline object needs when k_trim_ends is the dominant stage (c5); the other stages' in-region times stand.
@@ -823,12 +932,7 @@ def main(argv=None, rig=None):
         n_cu = int(torch.cuda.get_device_properties(dev).multi_processor_count) if dev.type == "cuda" else 256
     except Exception:
         pass
-    adapters = (ad_start, ad_end, ad_fasta)
-    out = None
     if rank == 0:
-        counters = counters_timed
-        v = abi.CountersView(counters, C, eng.n_adapters)
-        ms_per_step = dt / args.steps * 1e3
         # HBM bytes and vector wave-instructions per launch: PMC counters come from separate rocprofv3 --pmc passes of
         # this same command (profiles/kernel_counters.json records them per base, HBM bytes corrected as
         # MI355X_MICROARCH.md prescribes); --hbm-traffic overrides the dominant kernel's, null when nothing is recorded
@@ -867,57 +971,26 @@ def main(argv=None, rig=None):
         limited_by = "hbm"
         if issue and issue["frac_of_kernel_time"] > achieved / HBM_PEAK_GBS:
             limited_by = "valu_issue"
-        reads_ok = int(v.pre.reads) == args.steps * n * (world if world > 1 else 1) and \
-            int(v.pre.length_sum) == args.steps * total_bases
-        out = {
-            "metric": "Gbases/s processed (trim+cut+filter)",
-            "value": total_bases * args.steps / dt / 1e9,
-            "unit": "Gbases/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": "%s%s: BASELINE.json configs[%d] -- %d synthetic reads per GPU, %s, %s; inputs resident in HBM" % (
-                    args.workload, (" [ABLATION " + " ".join(filter(None, [args.set, args.median_len and "median-len=%d" % args.median_len])) + "]")
-                    if (args.set or args.median_len) else "", wl["config"], n, wl["reads_desc"], wl["flags"]),
-                "reads_per_gpu": n, "bases_per_gpu": n_bases, "max_read_len": max_len,
-                "parallelism": "shard%d (independent read shards, one RCCL all-reduce of the counters)" % world,
-                "pipelining": ("the steps are enqueued back to back on one stream; the end trims of step k + 1 run on a stream of their own beside "
-                               "k_scan of step k, two of their blocks per CU (fpl_assume_inputs_ready: the batch is resident), so "
-                               "kernel_ms.k_trim_ends is what is LEFT of them in line and kernel_ms.k_scan is k_scan WITH the trims beside it -- "
-                               "roofline.kernel_ms_alone / frac_alone: the same kernel with nothing beside it") if trim_ahead else "none: every kernel of a step in line",
-            },
-            "roofline": {
-                # priced against the HBM roofline as the contract prescribes (algorithmic bytes / kernel time / 8 TB/s);
-                # `limited_by` says what the counters say the kernel actually waits for
-                "bound": "hbm", "limited_by": limited_by, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src if traffic is not None else None,
-                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_BASE * n_bases,
-                "kernel_ms": {k: ktimes[k] / max(1, nbatches) for k in ktimes},
-                "kernel_ms_in_line": inline_ms,  # three steps behind the timed region with the trims NOT ahead: k_trim_ends' own duration
-                # the dominant kernel ALONE: the timed region runs it beside the next batch's end trims (two of their blocks per CU, each in the
-                # place of one of its five), which lengthens it; three in-line steps behind the region time it with nothing beside it
-                "kernel_ms_alone": (inline_ms or {}).get(dom), "frac_alone": (ALGO_BYTES_PER_BASE * n_bases / (inline_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                if inline_ms and inline_ms.get(dom) else None,
-                "duration_source": ("HIP events of the timed region" if not (inline_ms and dom == "k_trim_ends") else
-                                    "HIP events of three in-line steps behind the timed region (in the region the stage overlaps the step before); "
-                                    "with a FASTA list the stage is two launches, k_trim_ends_batched<8 words, chain> + k_trim_ends<2>"),
-                "issue": issue,
-                "path": {"what": "the whole launch sequence of a step against the same roofline: 2 B/base x bases / ms_per_step",
-                         "achieved": path_achieved, "frac": path_achieved / HBM_PEAK_GBS,
-                         "measured_bytes_per_base": (path_bytes / n_bases) if path_bytes else None,
-                         "ratio_to_algorithmic": (path_bytes / (ALGO_BYTES_PER_BASE * n_bases)) if path_bytes else None},
-            },
-            "counters_check": {"reads_in": int(v.pre.reads), "bases_in": int(v.pre.length_sum),
-                               "fragments_out": int(v.post.reads), "bases_out": int(v.post.length_sum),
-                               "expected_reads_in": args.steps * n * world if world > 1 else args.steps * n,
-                               "expected_bases_in": args.steps * total_bases, "ok": bool(reads_ok)},
+        out["roofline"] = {
+            # priced against the HBM roofline as the contract prescribes (algorithmic bytes / kernel time / 8 TB/s);
+            # `limited_by` says what the counters say the kernel actually waits for
+            "bound": "hbm", "limited_by": limited_by, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src if traffic is not None else None,
+            "algorithmic_bytes_per_launch": ALGO_BYTES_PER_BASE * n_bases,
+            "kernel_ms": {k: ktimes[k] / max(1, nbatches) for k in ktimes},
+            "kernel_ms_in_line": inline_ms,  # three steps behind the timed region with the trims NOT ahead: k_trim_ends' own duration
+            # the dominant kernel ALONE: the timed region runs it beside the next batch's end trims (two of their blocks per CU, each in the
+            # place of one of its five), which lengthens it; three in-line steps behind the region time it with nothing beside it
+            "kernel_ms_alone": (inline_ms or {}).get(dom), "frac_alone": (ALGO_BYTES_PER_BASE * n_bases / (inline_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS)
+            if inline_ms and inline_ms.get(dom) else None,
+            "duration_source": ("HIP events of the timed region" if not (inline_ms and dom == "k_trim_ends") else
+                                "HIP events of three in-line steps behind the timed region (in the region the stage overlaps the step before); "
+                                "with a FASTA list the stage is two launches, k_trim_ends_batched<8 words, chain> + k_trim_ends<2>"),
+            "issue": issue,
+            "path": {"what": "the whole launch sequence of a step against the same roofline: 2 B/base x bases / ms_per_step",
+                     "achieved": path_achieved, "frac": path_achieved / HBM_PEAK_GBS,
+                     "measured_bytes_per_base": (path_bytes / n_bases) if path_bytes else None,
+                     "ratio_to_algorithmic": (path_bytes / (ALGO_BYTES_PER_BASE * n_bases)) if path_bytes else None},
         }
         if args.parity_reads > 0:
             # ONE run of the oracle serves both: the checker of the timed batch's records / counters and -- at N = 1 -- the CPU

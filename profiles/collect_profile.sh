@@ -14,9 +14,9 @@ OUT=$ROOT/gpurun_out/$TAG
 W=$OUT/work_$WL
 rm -rf "$W"; mkdir -p "$W"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --workload $WL --cpu-bases 0 --e2e-reads 0 --parity-reads 0 $*"
+BENCH="python $ROOT/bench.py --full --workload $WL --cpu-bases 0 --e2e-reads 0 --parity-reads 0 $*"
 # (the bench line that is kept carries the parity sample; the profiled repeats leave it out)
-python $ROOT/bench.py --workload $WL --cpu-bases 0 --e2e-reads 0 $* --steps 10 --warmup 2 > "$OUT/bench_$WL.json" 2> "$W/bench.err"
+python $ROOT/bench.py --full --workload $WL --cpu-bases 0 --e2e-reads 0 $* --steps 10 --warmup 2 > "$OUT/bench_$WL.json" 2> "$W/bench.err"
 # 24 timed launches of every kernel behind 4 warm-up ones: kernel_stats_<wl>.csv is rocprofv3's own table over all 28,
 # kernel_stats_timed_<wl>.csv the same figures over the LAST 24 dispatches of every kernel (from the kernel trace) -- what
 # bench.py's HIP events bracket, so the two agree without a footnote about the warm-up launch

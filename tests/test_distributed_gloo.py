@@ -154,7 +154,7 @@ def _bench_rank(rank, world, port, outdir):
 
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--reads", "25", "--cpu-bases", "0",
+        bench.main(["--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--reads", "25", "--cpu-bases", "0",
                     "--e2e-reads", "0", "--full-json", os.path.join(outdir, "full_%d.json" % rank)], rig=rig)
     with open(os.path.join(outdir, "out_%d.txt" % rank), "w") as f:
         f.write(buf.getvalue())
@@ -208,7 +208,7 @@ def test_bench_line_is_one_short_json_line(orc, tmp_path, monkeypatch, capsys):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     full = tmp_path / "full.json"
-    bench.main(["--steps", "2", "--warmup", "1", "--reads", "30", "--cpu-bases", "1", "--e2e-reads", "0", "--full-json", str(full)], rig=rig)
+    bench.main(["--full", "--steps", "2", "--warmup", "1", "--reads", "30", "--cpu-bases", "1", "--e2e-reads", "0", "--full-json", str(full)], rig=rig)
     cap = capsys.readouterr()
     lines = [l for l in cap.out.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) < bench.LINE_LIMIT
@@ -236,3 +236,73 @@ def test_bench_line_is_one_short_json_line(orc, tmp_path, monkeypatch, capsys):
     l2 = json.loads(out2[0])
     assert l2["e2e"]["value"] == 15.4 and l2["e2e"]["to_file"] == 10.0 + names.index("to_file") and l2["e2e"]["large"]["null8"] is not None
     assert l2["roofline"] == line["roofline"] and l2["cpu_baseline"] == line["cpu_baseline"]
+
+
+def test_bench_plain_run_and_dump_outputs(orc, tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) times the steps and prints the contract fields and nothing of what --full adds;
+    --dump-outputs writes the last step's records and one step's counters as float arrays, the same from run to run,
+    equal to the oracle's for the batch the stand-in rig builds"""
+    import json
+
+    bench, rig = _stand_in_rig()
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    steps, reads = 3, 30
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        bench.main(["--steps", str(steps), "--warmup", "1", "--reads", str(reads), "--dump-outputs", str(d)], rig=rig)
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0]) < bench.LINE_LIMIT
+        line = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in line, k
+        for k in ("roofline", "cpu_baseline", "parity_sample", "e2e"):
+            assert k not in line, k
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        cc = line["counters_check"]
+        assert cc["ok"] is True and cc["reads_in"] == steps * reads
+        files = sorted(d.glob("*.npy"))
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    got = dumps[0]
+    seq, qual, off = synth.ont_like(reads, seed=1, median_len=500, p_middle=0.1)
+    C = int(np.diff(off.astype(np.int64)).max())
+    cfg = orc.Config(abi.FplOptions.default(**bench.WORKLOADS["c3_full_pipeline"]["opt"]), synth.START_ADAPTER, synth.END_ADAPTER)
+    want_res, want_cnt = orc.process_batch(cfg, seq, qual, off, max_cycles=C)
+    assert np.array_equal(got["records_read_index"], np.arange(reads))
+    for name in want_res.dtype.names:
+        if name != "reserved":
+            assert np.array_equal(got["records_" + name], want_res[name].astype(np.float64)), name
+    assert np.array_equal(got["counters_index"], np.arange(len(want_cnt)))
+    assert np.array_equal(got["counters"], want_cnt.astype(np.float64))
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path):
+    """outputs larger than the dump's limits: a fixed, seeded sample of the reads and of the counter entries, within 64 MB"""
+    _stand_in_rig()
+    import bench
+
+    n = bench.DUMP_READS * 3 + 7
+    rec = np.zeros(n, dtype=abi.RESULT_DTYPE)
+    rec["r1_len"] = np.arange(n)
+    rec["code"][:, 1] = np.arange(n) % 7
+    cnt = np.arange(bench.DUMP_COUNTERS * 2 + 5, dtype=np.int64) * 4
+    for d in ("a", "b"):
+        total = bench.dump_outputs(str(tmp_path / d), torch.from_numpy(rec.view(np.uint8).copy()), n, cnt, 4)
+        assert total <= bench.DUMP_LIMIT_BYTES
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").glob("*.npy")}
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    ridx = a["records_read_index"].astype(np.int64)
+    assert len(ridx) == bench.DUMP_READS and np.all(np.diff(ridx) > 0) and ridx[-1] < n
+    assert np.array_equal(a["records_r1_len"], ridx.astype(np.float64))
+    assert a["records_code"].shape == (bench.DUMP_READS, 2) and np.array_equal(a["records_code"][:, 1], ridx % 7)
+    cidx = a["counters_index"].astype(np.int64)
+    assert len(cidx) == bench.DUMP_COUNTERS and np.all(np.diff(cidx) > 0)
+    assert np.array_equal(a["counters"], cidx.astype(np.float64))

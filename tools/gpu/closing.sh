@@ -19,10 +19,10 @@ if [ $WHAT = all ] || [ $WHAT = profiles ]; then
   for wl in c3_full_pipeline c2_adapter_only c4_mixed c5_hifi64; do
     timeout 700 bash profiles/collect_profile.sh $TAG $wl > $O/collect_$wl.log 2>&1; tail -1 $O/collect_$wl.log
   done
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-  timeout 400 python bench.py --workload c5_hifi64 --steps 10 --warmup 2 --cpu-bases 0 --parity-reads 0 --e2e-reads 200000 --e2e-copies 0 > $O/bench_c5_e2e.json 2> $O/bench_c5_e2e.err
+  timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+  timeout 400 python bench.py --full --workload c5_hifi64 --steps 10 --warmup 2 --cpu-bases 0 --parity-reads 0 --e2e-reads 200000 --e2e-copies 0 > $O/bench_c5_e2e.json 2> $O/bench_c5_e2e.err
   timeout 600 bash tools/len_sweep.sh > $O/len_sweep.txt 2>&1; cat $O/len_sweep.txt
-  timeout 100 python bench.py --reads 1000000 --median-len 2000 --steps 5 --warmup 1 --cpu-bases 0 --e2e-reads 0 --parity-reads 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('1M x 2 kb:', round(d['value'],1), {k: round(v,2) for k,v in d['roofline']['kernel_ms'].items()})" | tee -a $O/len_sweep.txt
+  timeout 100 python bench.py --full --reads 1000000 --median-len 2000 --steps 5 --warmup 1 --cpu-bases 0 --e2e-reads 0 --parity-reads 0 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('1M x 2 kb:', round(d['value'],1), {k: round(v,2) for k,v in d['roofline']['kernel_ms'].items()})" | tee -a $O/len_sweep.txt
 fi
 if [ $WHAT = all ] || [ $WHAT = soak ]; then
   Q=$((SOAK / 4))

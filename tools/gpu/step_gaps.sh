@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$ROOT/gpurun_out/step_gaps; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python $ROOT/bench.py --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 6 --warmup 3 "$@" > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python $ROOT/bench.py --full --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 6 --warmup 3 "$@" > $OUT/log 2>&1
 python - $OUT <<'PY'
 import csv, glob, sys
 ev = []

@@ -6,7 +6,7 @@ TAG=${1:-timeline}; WL=${2:-c3_full_pipeline}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $ROOT/bench.py --workload $WL --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 6 --warmup 2 > "$OUT/bench_$WL.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $ROOT/bench.py --full --workload $WL --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 6 --warmup 2 > "$OUT/bench_$WL.log" 2>&1
 f=$(find /tmp/tl -name '*kernel_trace.csv' | head -1)
 python - "$f" "$OUT/timeline_$WL.csv" <<'P'
 import csv, sys

@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/memc
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --cpu-bases 0 --e2e-reads 0 --steps 2 --warmup 1 $*"
+B="python $ROOT/bench.py --full --cpu-bases 0 --e2e-reads 0 --steps 2 --warmup 1 $*"
 i=0
 for grp in "TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCP_LATENCY_sum" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "TCC_EA_RDREQ_sum TCC_EA_WRREQ_sum TCC_EA_RD_UNCACHED_32B_sum"; do
   i=$((i+1))

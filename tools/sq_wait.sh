@@ -1,7 +1,7 @@
 # measurement aid: what the waves of the three big kernels do with their cycles (SQ wave / wait / active counters, three --pmc passes of the c3 bench command; quad-cycles summed over the waves, millions per launch) -> gpurun_out/sqwait/summary.txt
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --workload c3_full_pipeline --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 2 --warmup 1"
+B="python $R/bench.py --full --workload c3_full_pipeline --cpu-bases 0 --e2e-reads 0 --parity-reads 0 --steps 2 --warmup 1"
 mkdir -p $R/gpurun_out/sqwait
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_RD" "SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CU_CYCLES SQ_INSTS_SMEM SQ_WAIT_INST_VMEM"; do
   n=$(echo $set | cut -d' ' -f1)
