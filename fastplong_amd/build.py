@@ -27,8 +27,9 @@ def _hipcc():
 
 
 def hip_sources():
-    return [os.path.join(CSRC, f) for f in ("fpl_hip.hip", "kernels.h", "pipeline.h", "dev_prims.h", "dev_types.h", "adapter_pick.h")] + [
-        os.path.join(ROOT, "include", "fastplong_amd.h")]
+    """fpl_hip.hip first (the one translation unit), then every header it may include"""
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    return [os.path.join(CSRC, "fpl_hip.hip")] + hdrs + [os.path.join(ROOT, "include", "fastplong_amd.h")]
 
 
 def build_hip(force=False, verbose=False):

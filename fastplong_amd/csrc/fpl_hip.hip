@@ -20,6 +20,7 @@
 
 #include "pipeline.h"
 #include "text_parse.h"
+#include "bam_decode.h"
 
 using namespace fpl;
 
@@ -111,6 +112,11 @@ struct fpl_ctx {
         u32 h_line_cap = 0;
         uint64_t text_bytes = 0;
         hipEvent_t ev_parsed = nullptr;
+        /* a BAM batch (fpl_process_bam_async): the inflated record bytes and where every record starts; a CSR batch otherwise */
+        u8* d_bam = nullptr;
+        uint64_t bam_cap = 0;
+        uint64_t* d_rec = nullptr;
+        u32 rec_st_cap = 0;
     };
     Slot slot[FPL_MAX_IN_FLIGHT];
     u32 submitted = 0, waited = 0; /* batches handed to / collected from the asynchronous path */
@@ -287,7 +293,7 @@ void fpl_destroy(fpl_ctx* ctx) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& sl : ctx->slot) {
-        void* sp[] = {sl.d_seq, sl.d_qual, sl.d_off, sl.d_results, sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len, sl.d_hdr};
+        void* sp[] = {sl.d_seq, sl.d_qual, sl.d_off, sl.d_results, sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len, sl.d_hdr, sl.d_bam, sl.d_rec};
         for (void* p : sp)
             if (p) (void)hipFree(p);
         if (sl.h_results) (void)hipHostFree(sl.h_results);
@@ -1183,6 +1189,159 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
     }
     ctx->submitted++;
     return FPL_OK;
+}
+
+/* ---- BAM records in (ABI v8): csrc/bam_decode.h ---- */
+/* what the decode kernel will read of every record lies inside [0, n_bytes): the fixed fields, the name, the CIGAR, the bases and
+   the qualities; l_seq agrees with the CSR offsets.  (The host walked the records already -- this is the library's own bounds
+   check, 24 bytes per record, so that no caller can make the kernel read outside the upload.) */
+static int bam_check(const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off, u32 n_reads, u32* max_len) {
+    u32 ml = 0;
+    for (u32 i = 0; i < n_reads; i++) {
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7FFFFFFFull) return FPL_ERR_ARG;
+        const uint64_t rs = rec_start[i];
+        if (rs > n_bytes || n_bytes - rs < 36) return FPL_ERR_ARG;
+        const uint8_t* r = bam + rs;
+        const uint64_t l_name = r[12], n_cigar = (uint64_t)r[16] | ((uint64_t)r[17] << 8);
+        uint32_t l_seq;
+        memcpy(&l_seq, r + 20, 4);
+        if (l_seq > 0x7FFFFFFFu || (uint64_t)l_seq != off[i + 1] - off[i]) return FPL_ERR_ARG;
+        const uint64_t need = 36 + l_name + 4 * n_cigar + ((uint64_t)l_seq + 1) / 2 + l_seq;
+        if (n_bytes - rs < need) return FPL_ERR_ARG;
+        if (l_seq > ml) ml = l_seq;
+    }
+    if (max_len) *max_len = ml;
+    return FPL_OK;
+}
+
+/* enqueue the decode of a batch whose records, record starts and offsets are on the device (stream st) */
+static void bam_launch(const u8* d_bam, const uint64_t* d_rec, const uint64_t* d_off, u32 n_reads, uint64_t o_begin, uint64_t o_end,
+                       u8* d_seq, u8* d_qual, hipStream_t st) {
+    u64 word0, n_words;
+    bam_words(o_begin, o_end, word0, n_words);
+    if (!n_words) return;
+    const u64 blocks = (n_words + BAM_THREADS - 1) / BAM_THREADS;
+    hipLaunchKernelGGL(k_bam_decode, dim3((u32)blocks), dim3(BAM_THREADS), 0, st, d_bam, d_rec, d_off, n_reads, word0, n_words, d_seq,
+                       d_qual);
+}
+
+int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off,
+                          uint32_t n_reads, uint8_t* seq_out, uint8_t* qual_out, fpl_read_result* results) {
+    if (!ctx) return FPL_ERR_ARG;
+    if (n_reads && (!bam || !rec_start || !off || !seq_out || !qual_out || !results)) return FPL_ERR_ARG;
+    if (ctx->submitted - ctx->waited >= FPL_MAX_IN_FLIGHT) return FPL_ERR_STATE;
+    FPL_HIP(hipSetDevice(ctx->device));
+    if (ctx->hcfg.defer && ctx->submitted != ctx->waited) return FPL_ERR_STATE; /* (--break / --mask: as fpl_process_batch_async) */
+    u32 max_len = 0;
+    if (n_reads && bam_check(bam, n_bytes, rec_start, off, n_reads, &max_len) != FPL_OK) {
+        ctx->err = "fpl_process_bam_async: a record does not lie inside the bytes given, or its l_seq disagrees with the offsets";
+        return FPL_ERR_ARG;
+    }
+    fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
+    sl.kind = 0; /* (collected by fpl_wait like a CSR batch) */
+    sl.n_reads = n_reads;
+    sl.user_results = results;
+    sl.rc = FPL_OK;
+    if (n_reads == 0) {
+        ctx->submitted++;
+        return FPL_OK;
+    }
+    const uint64_t o_begin = off[0], o_end = off[n_reads];
+    int r = ensure_host_streams(ctx);
+    if (r != FPL_OK) return r;
+    r = ensure_slot(ctx, sl, n_reads, o_end + 16); /* (the decode writes whole 16-byte words) */
+    if (r != FPL_OK) return r;
+    if (n_bytes + BAM_PAD > sl.bam_cap || !sl.d_bam) {
+        FPL_HIP(hipDeviceSynchronize());
+        if (sl.d_bam) (void)hipFree(sl.d_bam);
+        sl.d_bam = nullptr;
+        sl.bam_cap = 0;
+        const uint64_t cap = n_bytes + n_bytes / 4 + BAM_PAD;
+        FPL_HIP(hipMalloc((void**)&sl.d_bam, cap));
+        sl.bam_cap = cap;
+    }
+    if (n_reads > sl.rec_st_cap || !sl.d_rec) {
+        FPL_HIP(hipDeviceSynchronize());
+        if (sl.d_rec) (void)hipFree(sl.d_rec);
+        sl.d_rec = nullptr;
+        sl.rec_st_cap = 0;
+        const u32 cap = n_reads + n_reads / 4 + 16;
+        FPL_HIP(hipMalloc((void**)&sl.d_rec, sizeof(uint64_t) * (size_t)cap));
+        sl.rec_st_cap = cap;
+    }
+    auto enqueue = [&]() -> int {
+        /* the upload on the copy stream, the decode on the parse stream behind it (the next batch's upload goes out meanwhile), the
+           per-read kernels behind the decode; the records, bases and qualities come back on the way-back stream */
+        FPL_HIP(hipMemcpyAsync(sl.d_bam, bam, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(sl.d_rec, rec_start, sizeof(uint64_t) * (size_t)n_reads, hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(sl.d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
+        FPL_HIP(hipStreamWaitEvent(ctx->s_parse, sl.ev_h2d, 0));
+        bam_launch(sl.d_bam, sl.d_rec, sl.d_off, n_reads, o_begin, o_end, sl.d_seq, sl.d_qual, ctx->s_parse);
+        FPL_HIP(hipGetLastError());
+        FPL_HIP(hipEventRecord(sl.ev_parsed, ctx->s_parse));
+        FPL_HIP(hipStreamWaitEvent(ctx->stream, sl.ev_parsed, 0));
+        ctx->next_inputs_event = sl.ev_parsed; /* (the end trims may start as soon as the bases are decoded) */
+        const int rd = fpl_process_batch_device(ctx, sl.d_seq, sl.d_qual, sl.d_off, n_reads, o_end, max_len, sl.d_results, ctx->stream);
+        ctx->next_inputs_event = nullptr;
+        if (rd != FPL_OK) return rd;
+        FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
+        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_parsed, 0));
+        if (o_end > o_begin) {
+            FPL_HIP(hipMemcpyAsync(seq_out + o_begin, sl.d_seq + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
+            FPL_HIP(hipMemcpyAsync(qual_out + o_begin, sl.d_qual + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
+        }
+        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_kern, 0));
+        FPL_HIP(hipMemcpyAsync(sl.h_results, sl.d_results, sizeof(fpl_read_result) * (size_t)n_reads, hipMemcpyDeviceToHost,
+                               ctx->s_d2h));
+        FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
+        return FPL_OK;
+    };
+    r = enqueue();
+    if (r != FPL_OK) {
+        if (ctx->s_h2d) (void)hipStreamSynchronize(ctx->s_h2d);
+        if (ctx->s_parse) (void)hipStreamSynchronize(ctx->s_parse);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->s_d2h) (void)hipStreamSynchronize(ctx->s_d2h);
+        return r;
+    }
+    ctx->submitted++;
+    return FPL_OK;
+}
+
+int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off, uint32_t n_reads,
+                   uint8_t* seq_out, uint8_t* qual_out) {
+    if (n_reads == 0) return FPL_OK;
+    if (!bam || !rec_start || !off || !seq_out || !qual_out || device < 0) return FPL_ERR_ARG;
+    if (bam_check(bam, n_bytes, rec_start, off, n_reads, nullptr) != FPL_OK) return FPL_ERR_ARG;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return FPL_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return FPL_ERR_HIP;
+    const uint64_t o_begin = off[0], o_end = off[n_reads];
+    u8 *d_bam = nullptr, *d_seq = nullptr, *d_qual = nullptr;
+    uint64_t *d_rec = nullptr, *d_off = nullptr;
+    const size_t out_bytes = (size_t)((o_end + 15) & ~15ull);
+    int rc = FPL_OK;
+    if (hipMalloc((void**)&d_bam, n_bytes + BAM_PAD) != hipSuccess || hipMalloc((void**)&d_rec, sizeof(uint64_t) * n_reads) != hipSuccess ||
+        hipMalloc((void**)&d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)) != hipSuccess ||
+        hipMalloc((void**)&d_seq, out_bytes + 16) != hipSuccess || hipMalloc((void**)&d_qual, out_bytes + 16) != hipSuccess)
+        rc = FPL_ERR_HIP;
+    if (rc == FPL_OK &&
+        (hipMemcpy(d_bam, bam, n_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(d_rec, rec_start, sizeof(uint64_t) * n_reads, hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice) != hipSuccess))
+        rc = FPL_ERR_HIP;
+    if (rc == FPL_OK) {
+        bam_launch(d_bam, d_rec, d_off, n_reads, o_begin, o_end, d_seq, d_qual, 0);
+        if (hipGetLastError() != hipSuccess) rc = FPL_ERR_HIP;
+    }
+    if (rc == FPL_OK && o_end > o_begin &&
+        (hipMemcpy(seq_out + o_begin, d_seq + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess ||
+         hipMemcpy(qual_out + o_begin, d_qual + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = FPL_ERR_HIP;
+    for (void* p : {(void*)d_bam, (void*)d_rec, (void*)d_off, (void*)d_seq, (void*)d_qual})
+        if (p) (void)hipFree(p);
+    return rc;
 }
 
 int fpl_process_batch(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, uint32_t n_reads,

@@ -24,6 +24,7 @@ EXPORTS = [
     "fpl_process_batch_async", "fpl_wait", "fpl_in_flight", "fpl_host_alloc", "fpl_host_free", "fpl_allreduce_counters",
     "fpl_count_end_kmers", "fpl_pick_adapter", "fpl_rccl_library", "fpl_comm_init", "fpl_get_batch_forms", "fpl_assume_inputs_ready",
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
+    "fpl_process_bam_async", "fpl_decode_bam",
 ]
 
 
@@ -130,11 +131,33 @@ def load_library(path=None):
     L.fpl_cancel_text.argtypes = [C.c_void_p]
     L.fpl_wait_text.restype = C.c_int
     L.fpl_wait_text.argtypes = [C.c_void_p, C.POINTER(abi.FplTextResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.fpl_process_bam_async.restype = C.c_int
+    L.fpl_process_bam_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    L.fpl_decode_bam.restype = C.c_int
+    L.fpl_decode_bam.argtypes = [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
         _lib = L
     return L
+
+
+def decode_bam(device, bam, rec_start, off):
+    """fpl_decode_bam (no context): inflated BAM record bytes, record starts, output CSR offsets -> (bases, qualities)"""
+    L = load_library()
+    bam = np.ascontiguousarray(bam, dtype=np.uint8)
+    rec_start = np.ascontiguousarray(rec_start, dtype=np.uint64)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(off) - 1
+    total = int(off[-1]) if n >= 0 and len(off) else 0
+    seq = np.zeros(max(total, 1), np.uint8)
+    qual = np.zeros(max(total, 1), np.uint8)
+    rc = L.fpl_decode_bam(int(device), bam.ctypes.data, len(bam), rec_start.ctypes.data, off.ctypes.data, max(n, 0), seq.ctypes.data,
+                          qual.ctypes.data)
+    if rc != abi.FPL_OK:
+        raise FplError("fpl_decode_bam: %s" % L.fpl_strerror(rc).decode())
+    return seq[:total], qual[:total]
 
 
 def _b(s):
@@ -210,6 +233,19 @@ class Engine:
 
     def wait(self):
         self._check(self.L.fpl_wait(self.h), "fpl_wait")
+
+    def submit_bam(self, bam, rec_start, off, seq_out, qual_out, res):
+        """fpl_process_bam_async: inflated BAM record bytes (uint8, with at least one addressable byte), where each record
+        starts (uint64), the output CSR offsets (uint64, n + 1); the decoded bases and qualities land in seq_out / qual_out
+        (pinned_array views of >= off[-1] bytes) and the records in res.  Everything must stay alive until wait()."""
+        n = len(off) - 1
+        self._keep_bam = (getattr(self, "_keep_bam", []) + [(bam, rec_start, off)])[-(abi.FPL_MAX_IN_FLIGHT + 1):]
+        self._check(self.L.fpl_process_bam_async(self.h, bam.ctypes.data, len(bam), rec_start.ctypes.data, off.ctypes.data, n,
+                                                 seq_out.ctypes.data, qual_out.ctypes.data, res.ctypes.data), "fpl_process_bam_async")
+
+    def decode_bam(self, bam, rec_start, off):
+        """fpl_decode_bam on this engine's device -> (bases, qualities) as uint8 arrays of off[-1] bytes"""
+        return decode_bam(self.device, bam, rec_start, off)
 
     def submit_text(self, text):
         """fpl_process_text_async: a chunk of FASTQ text (a pinned uint8 array: pinned_array) that starts at a record and ends

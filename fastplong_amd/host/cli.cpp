@@ -39,7 +39,10 @@
 #include <thread>
 #include <vector>
 
+#include <dlfcn.h>
+
 #include "fastplong_amd.h"
+#include "bam.h"
 #include "evaluator.h"
 #include "fastq.h"
 #include "report.h"
@@ -453,11 +456,30 @@ int main(int argc, char* argv[]) {
     const double launchToMain = since_launch();
     /* Evaluator::evaluateSeqLenAndCheckRNA, src/evaluator.cpp:16-61: U vs T in the first 100 reads */
     bool isRNA = false;
+    /* BAM input (host/bam.h): recognised by its content; its bases are decoded on the device.  The two entry points are looked up at
+       run time -- the binary must start against a library without them (the test stand-ins) as long as the input is FASTQ */
+    const bool bamIn = !fromStdin && in != "/dev/stdin" && fplh::is_bam_file(in);
+    typedef int (*BamAsyncFn)(fpl_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*,
+                              fpl_read_result*);
+    typedef int (*BamDecodeFn)(int32_t, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*);
+    BamAsyncFn bamAsync = nullptr;
+    if (bamIn) {
+        bamAsync = (BamAsyncFn)dlsym(RTLD_DEFAULT, "fpl_process_bam_async");
+        BamDecodeFn bamDecode = (BamDecodeFn)dlsym(RTLD_DEFAULT, "fpl_decode_bam");
+        if (!bamAsync || !bamDecode)
+            error_exit("BAM input needs fpl_process_bam_async and fpl_decode_bam (C-ABI version 8), which the loaded libfastplong_amd.so lacks");
+        fplh::set_bam_decoder([bamDecode](const uint8_t* bam, uint64_t nb, const uint64_t* rec, const uint64_t* of, uint32_t n, uint8_t* sq,
+                                          uint8_t* ql) { return bamDecode(0, bam, nb, rec, of, n, sq, ql) == FPL_OK; });
+    }
     if (!fromStdin && in != "/dev/stdin") {
-        fplh::FastqReader ev(in);
-        if (!ev.ok()) error_exit("Failed to open file: " + in);
         fplh::Batch b;
-        ev.fill(b, ~0ull, 100);
+        if (bamIn) {
+            fplh::read_bam_prefix(in, b, 100, 1L << 62);
+        } else {
+            fplh::FastqReader ev(in);
+            if (!ev.ok()) error_exit("Failed to open file: " + in);
+            ev.fill(b, ~0ull, 100);
+        }
         long numT = 0, numU = 0;
         for (uint8_t c : b.seq) {
             numT += c == 'T';
@@ -553,7 +575,7 @@ int main(int argc, char* argv[]) {
     const char* chunkMem = nullptr; /* the input's text in memory (a mapping of the file / inflated gzip members) instead of a descriptor */
     bool chunkMemMapped = false;    /* ... a file mapping: its pages go back to the kernel as the reader passes them */
     uint64_t chunkFileSize = 0;
-    if (!fromStdin && in != "/dev/stdin" && readsToProcess == 0 && !getenv("FPLH_NO_CHUNKS")) {
+    if (!bamIn && !fromStdin && in != "/dev/stdin" && readsToProcess == 0 && !getenv("FPLH_NO_CHUNKS")) {
         const int fd = open(in.c_str(), O_RDONLY);
         struct stat st;
         unsigned char magic[2] = {0, 0};
@@ -624,6 +646,7 @@ int main(int argc, char* argv[]) {
         cerr << "WARNING: --batch_mbases / --batch_reads do not apply to this input: its batches are the chunks of --chunk_mb ("
              << (chunkBytes >> 20) << " MB of text each); lower --chunk_mb for smaller batches" << endl;
     fplh::FastqReader* reader = nullptr;
+    fplh::BamReader* bamReader = nullptr; /* BAM input: batches of --chunk_mb of inflated records */
     /* Work objects bound what is in flight: one per parser, FPL_MAX_IN_FLIGHT per device in the copy / kernel stage,
        one per device being formatted, two waiting for the writer */
     auto gz_name = [](const string& p) { return p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0; };
@@ -645,7 +668,10 @@ int main(int argc, char* argv[]) {
         fplh::ByteBuf::set_arena((size_t)(chunkBytes + (5u << 20)), (size_t)nWork);
     else if (chunked) /* a chunk holds about half its bytes in bases: one block each for the bases and the qualities of a batch */
         fplh::ByteBuf::set_arena((size_t)(chunkBytes / 2 + chunkBytes / 16 + (2u << 20)), 2 * (size_t)nWork);
-    if (!chunked) {
+    if (bamIn) {
+        bamReader = new fplh::BamReader(in);
+        if (!bamReader->ok()) error_exit("Failed to open file: " + in);
+    } else if (!chunked) {
         reader = new fplh::FastqReader(in);
         if (!reader->ok()) error_exit("Failed to open file: " + in);
         /* threads of the reader's refill / locate / copy phases (FPLH_PARSE_THREADS overrides) */
@@ -797,7 +823,27 @@ int main(int argc, char* argv[]) {
 
     /* ---- stage 1: batches in input order -> devq (round-robin over the devices) */
     thread readerThread([&]() {
-        if (!chunked) {
+        if (bamReader) {
+            for (;;) {
+                uint32_t maxReads = 0x3FFFFFFFu;
+                if (readsLeft >= 0) maxReads = (uint32_t)min<long>(readsLeft, maxReads);
+                if (maxReads == 0) break;
+                Work* w = freeq.pop();
+                w->batch.clear();
+                const double t0 = now();
+                const uint32_t got = bamReader->fill(w->batch, chunkBytes, maxReads);
+                tParse += now() - t0;
+                if (got == 0) {
+                    freeq.push(w);
+                    break;
+                }
+                if (readsLeft >= 0) readsLeft -= w->batch.n();
+                w->seq_no = nBatches++;
+                devq[w->seq_no % nGpus].push(w);
+            }
+            if (!bamReader->warning().empty()) cerr << bamReader->warning() << endl;
+            if (!bamReader->error().empty()) ioError = bamReader->error();
+        } else if (!chunked) {
             for (;;) {
                 uint32_t maxReads = batchReads;
                 if (readsLeft >= 0) maxReads = (uint32_t)min<long>(readsLeft, maxReads);
@@ -1041,6 +1087,9 @@ int main(int argc, char* argv[]) {
                     const bool text = w->batch.text_backed;
                     if (text)
                         w->rc = fpl_process_text_async(ctx, w->batch.raw.data() + w->batch.raw_begin, w->batch.raw_len);
+                    else if (w->batch.bam_backed) /* (the device decodes the bases into the batch's own page-locked arrays) */
+                        w->rc = bamAsync(ctx, w->batch.bam.data(), w->batch.bam.size(), w->batch.rec_start.data(), w->batch.off.data(),
+                                         w->batch.n(), w->batch.seq.data(), w->batch.qual.data(), w->res.data());
                     else
                         w->rc = fpl_process_batch_async(ctx, w->batch.seq.data(), w->batch.qual.data(), w->batch.off.data(), w->batch.n(),
                                                         w->res.data());

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../csrc/adapter_pick.h"
+#include "bam.h"
 #include "fastq.h"
 
 using namespace std;
@@ -174,7 +175,69 @@ long read_prefix(FastqReader& reader, Batch& b, long read_limit, long base_limit
 
 }  // namespace
 
+static BamDecoder g_bam_decoder;
+void set_bam_decoder(BamDecoder f) { g_bam_decoder = std::move(f); }
+
+long read_bam_prefix(const string& path, Batch& b, long read_limit, long base_limit) {
+    BamReader rd(path);
+    if (!rd.ok()) return 0;
+    b.clear();
+    /* the first record alone (where the reference's count of bytes starts), then the rest of the prefix */
+    if (rd.fill(b, ~0ull, 1) == 0) {
+        if (!rd.error().empty()) {
+            cerr << "ERROR: " << rd.error() << endl;
+            exit(-1);
+        }
+        return 0;
+    }
+    const uint64_t first_end = rd.compressed_pulled();
+    Batch rest;
+    if (read_limit > 1 && (long)b.off.back() < base_limit) rd.fill(rest, ~0ull, (uint32_t)(read_limit - 1), (uint64_t)base_limit - b.off.back());
+    if (!rd.error().empty()) {
+        cerr << "ERROR: " << rd.error() << endl;
+        exit(-1);
+    }
+    /* one batch out of the two: the records of `rest` behind the first */
+    const uint32_t n1 = rest.n();
+    const uint64_t shift = b.bam.size();
+    b.bam.reserve(shift + rest.bam.size());
+    b.bam.resize_uninit(shift + rest.bam.size());
+    if (rest.bam.size()) memcpy(b.bam.data() + shift, rest.bam.data(), rest.bam.size());
+    const uint64_t base_off = b.off.back(), text_off = b.text.size();
+    b.text.insert(b.text.end(), rest.text.begin(), rest.text.end());
+    for (uint32_t i = 0; i < n1; i++) {
+        b.rec_start.push_back(shift + rest.rec_start[i]);
+        b.off.push_back(base_off + rest.off[i + 1]);
+        b.name_off.push_back(text_off + rest.name_off[i + 1]);
+        b.name_len.push_back(rest.name_len[i]);
+        b.strand_len.push_back(rest.strand_len[i]);
+    }
+    const long records = b.n();
+    b.seq.resize_uninit(b.off.back());
+    b.qual.resize_uninit(b.off.back());
+    if (!g_bam_decoder) {
+        cerr << "ERROR: BAM input: no decoder for the evaluation prefix (the device library's fpl_decode_bam)" << endl;
+        exit(-1);
+    }
+    if (records && !g_bam_decoder(b.bam.data(), b.bam.size(), b.rec_start.data(), b.off.data(), (uint32_t)records, b.seq.data(),
+                                  b.qual.data())) {
+        cerr << "ERROR: BAM input: decoding the evaluation prefix failed (fpl_decode_bam)" << endl;
+        exit(-1);
+    }
+    const bool reached_eof = records < read_limit && (long)b.off.back() < base_limit;
+    if (reached_eof) return records;
+    const uint64_t last_end = rd.compressed_pulled();
+    const double bytesPerRead = (double)(last_end - first_end) / (double)records;
+    const double est = (double)rd.file_size() * 1.01 / bytesPerRead;
+    if (!(est < 9.2e18)) return (long)0x8000000000000000ull;
+    return (long)est;
+}
+
 long evaluate_read_num(const string& path) {
+    if (is_bam_file(path)) {
+        Batch b;
+        return read_bam_prefix(path, b, 512 * 1024, 151L * 512 * 1024);
+    }
     FastqReader reader(path);
     if (!reader.ok()) return 0;
     Batch b;
@@ -215,10 +278,15 @@ void detect_adapters(const string& path, int trim_tail, bool is_rna, string& sta
     if (start != "auto" && end != "auto") return;
     const long READ_LIMIT = 64 * 1024;
     const long BASE_LIMIT = 8192 * READ_LIMIT;
-    FastqReader reader(path);
-    if (!reader.ok()) return;
     Batch b;
-    const long rn = read_prefix(reader, b, READ_LIMIT, BASE_LIMIT, path);
+    long rn = 0;
+    if (is_bam_file(path)) {
+        rn = read_bam_prefix(path, b, READ_LIMIT, BASE_LIMIT);
+    } else {
+        FastqReader reader(path);
+        if (!reader.ok()) return;
+        rn = read_prefix(reader, b, READ_LIMIT, BASE_LIMIT, path);
+    }
     if (read_num) *read_num = rn;
     const long records = b.n();
     if (records < 100) return; /* we need at least 100 valid records to evaluate */

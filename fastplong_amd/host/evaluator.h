@@ -38,6 +38,17 @@ struct AdapterVerdict {
 using AdapterPicker = std::function<bool(const uint8_t*, const uint64_t*, uint32_t, int side, int shift_tail, bool is_rna, AdapterVerdict&)>;
 void set_adapter_picker(AdapterPicker f);
 
+/* BAM input (host/bam.h): the evaluation prefix's bases are decoded by this call (the CLI: the C-ABI's fpl_decode_bam on the
+ * first device) -- bam, n_bytes, record starts, CSR offsets, n_reads, bases out, qualities out; false when it could not run.  The
+ * host has no decoder of its own: without one, a BAM input cannot be evaluated and the process ends with an error. */
+using BamDecoder = std::function<bool(const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*)>;
+void set_bam_decoder(BamDecoder f);
+class BamReader;
+struct Batch;
+/* up to read_limit records / base_limit bases of a BAM input, decoded (b: a CSR batch afterwards); the read-count estimate
+ * of Evaluator::evaluateReadNum (src/evaluator.cpp:63-103) over the file's compressed bytes */
+long read_bam_prefix(const std::string& path, Batch& b, long read_limit, long base_limit);
+
 std::string int2seq(unsigned int val, int seqlen, bool is_rna = false);
 int seq2int(const char* seq, int rlen, int pos, int keylen, int last_val = -1);
 

@@ -633,6 +633,9 @@ void Batch::clear() {
     raw_begin = raw_len = 0;
     line.clear();
     text_backed = false;
+    bam.clear();
+    rec_start.clear();
+    bam_backed = false;
 }
 
 void Batch::adopt_lines(const uint32_t* ls, uint32_t n_records) {

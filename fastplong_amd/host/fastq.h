@@ -80,6 +80,12 @@ struct Batch {
     uint64_t raw_begin = 0, raw_len = 0;
     std::vector<uint32_t> line;
     bool text_backed = false;
+    /* A BAM-BACKED batch (host/bam.h): `bam` holds inflated BAM records as they lie in the file, rec_start where each read's
+       record starts in it; off / names are filled by the host's walk, seq / qual are sized for the bases and receive them from
+       the device (fpl_process_bam_async), after which the batch is an ordinary CSR batch. */
+    ByteBuf bam;
+    std::vector<uint64_t> rec_start;
+    bool bam_backed = false;
     uint32_t n() const { return off.empty() ? 0 : (uint32_t)(off.size() - 1); }
     bool has_records() const { return n() > 0 || (text_backed && raw_len > 0); }
     /* the four lines of read i, whichever form the batch has */

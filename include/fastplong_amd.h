@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define FPL_ABI_VERSION 7
+#define FPL_ABI_VERSION 8
 
 /* limits */
 #define FPL_MAX_ADAPTER_LEN 255 /* longest adapter the device path accepts            */
@@ -347,6 +347,37 @@ int fpl_peek_text(fpl_ctx* ctx, fpl_text_result* out);
 int fpl_start_text(fpl_ctx* ctx);
 int fpl_cancel_text(fpl_ctx* ctx);
 int fpl_wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts);
+
+/*
+ * (ABI v8) BAM records in: the host inflates a BAM's BGZF blocks and walks its records (24 bytes of each: where it starts, its
+ * flag, l_seq); the device decodes the packed bases and the qualities (fastplong_amd/csrc/bam_decode.h).  The link carries the
+ * packed form up (1.5 bytes per base: half a byte of base, one of quality) and the decoded one back (2 bytes per base, beside the
+ * uploads of the next batches on a full-duplex link).  What a record becomes is `samtools fastq`'s twin of it:
+ * bases from the 4-bit codes "=ACMGRSVTWYHKDBN" (high nibble first), qualities min(phred, 93) + 33, and for flag 0x10 the bases
+ * reverse-complemented (the complement of a code is its four bits reversed) and the qualities reversed.  Which records are
+ * passed (secondary / supplementary ones are not), and every check of the file's structure, are the caller's.
+ *
+ *   bam        the inflated record bytes, n_bytes of them (page-locked memory recommended);
+ *   rec_start  n_reads byte offsets into bam: where record i starts (at its block_size field);
+ *   off        n_reads + 1 CSR offsets of the output, off[i + 1] - off[i] = l_seq of record i (off[0] may be > 0);
+ *   seq_out, qual_out  receive the ASCII bases / qualities of read i at [off[i], off[i + 1]) -- caller-owned arrays of at least
+ *              off[n_reads] bytes; for fpl_process_bam_async they must be page-locked (fpl_host_alloc), the device writes them.
+ * Every record must lie inside [0, n_bytes) -- fixed fields, name, CIGAR, bases, qualities -- and its l_seq agree with off:
+ * the library checks this on the calling thread (FPL_ERR_ARG otherwise; nothing is enqueued).
+ *
+ *   fpl_process_bam_async  the BAM form of fpl_process_batch_async: takes one of the FPL_MAX_IN_FLIGHT slots, keeps the FIFO order
+ *              and is collected by fpl_wait(), after which results[i], seq_out and qual_out hold the batch exactly as if the decoded
+ *              arrays had been submitted through fpl_process_batch_async (--break / --mask fragment lists included: fpl_get_fragments
+ *              after the wait).  bam, rec_start and off must stay valid, and seq_out / qual_out / results untouched, until the
+ *              batch has been waited for.
+ *   fpl_decode_bam  decode only, no context, synchronous (like fpl_count_end_kmers): the evaluation prefix of a BAM input --
+ *              RNA check, adapter detection, read-count estimate -- runs before any context exists.  Any host memory; nothing is
+ *              kept after the call returns.
+ */
+int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off,
+                          uint32_t n_reads, uint8_t* seq_out, uint8_t* qual_out, fpl_read_result* results);
+int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off, uint32_t n_reads,
+                   uint8_t* seq_out, uint8_t* qual_out);
 
 /* Page-locked host memory for the arrays handed to fpl_process_batch[_async] / fpl_process_text_async: the DMA engines read it
  * directly.  Blocks of 8 MB and more are anonymous memory on transparent huge pages, touched and registered with the runtime

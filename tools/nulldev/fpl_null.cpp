@@ -255,6 +255,11 @@ const char* fpl_rccl_library(void) { return ""; }
 int fpl_comm_init(fpl_ctx**, int32_t) { return FPL_OK; }
 int fpl_count_end_kmers(int32_t, const uint8_t*, const uint64_t*, uint32_t, int32_t, int32_t, uint32_t*, uint64_t*, uint64_t*) { return FPL_ERR_NO_DEVICE; }
 int fpl_pick_adapter(int32_t, const uint8_t*, const uint64_t*, uint32_t, int32_t, int32_t, int32_t, fpl_adapter_pick*) { return FPL_ERR_NO_DEVICE; }
+/* (BAM input is decoded on the device: the null device has none to decode with) */
+int fpl_process_bam_async(fpl_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*, fpl_read_result*) {
+    return FPL_ERR_NO_DEVICE;
+}
+int fpl_decode_bam(int32_t, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*) { return FPL_ERR_NO_DEVICE; }
 int fpl_reset_counters(fpl_ctx* ctx) {
     if (!ctx) return FPL_ERR_ARG;
     ctx->reads = ctx->bases = 0;
