@@ -10,9 +10,13 @@
  * rolling key coder they call (Evaluator::seq2int, src/evaluator.cpp:503-560) -- what fpl_count_end_kmers / fpl_pick_adapter are
  * checked against on the GPU.
  *
- * Parity status: UNPINNED.  src/evaluator.cpp includes the FASTQ reader and through it ISA-L headers this image lacks, so the
- * real object cannot be compiled here; the reference's only known-answer test for this file (test/evaluator_test.cpp) covers
- * int2seq / seq2int, not these two functions.  What this file gives is an independent SECOND reading of the reference.
+ * Parity status: UNPINNED as a function.  src/evaluator.cpp includes the FASTQ reader and through it ISA-L; with the
+ * declaration stand-in of oracle/standin/isa-l the whole reference program builds (oracle/_ref/fastplong_ref), and its
+ * detection is compared with the CLI's on planted DNA and RNA input (one clear winner each): on the stub library through
+ * host/evaluator.cpp (tests/test_cli_vs_ref_binary_stub.py), on the GPU through fpl_pick_adapter, which is checked against
+ * this file (tests/test_gpu_vs_ref_binary.py).  getTopKey's tie and count-digit rules do not reach the reference that way.
+ * The reference's only known-answer test for this file (test/evaluator_test.cpp) covers int2seq / seq2int.  What this file
+ * gives for those rules is an independent SECOND reading of the reference.
  */
 #include <stdint.h>
 #include <string.h>

@@ -17,9 +17,11 @@
  *   - the --break / --mask stage (Filter::detectLowQualityRegions, Read::breakByRegions,
  *     Read::maskRegionWithN as processSingleEnd chains them, src/seprocessor.cpp:234-262) is
  *     cross-checked the same way (harness commands LQR / BRK);
- *   - AdapterTrimmer (src/adaptertrimmer.cpp) includes Google Highway, which this image
- *     does not have, so that one file is unbuildable here: for it the restatement is pinned
- *     by the reference's own four known-answer tests only (test/adaptertrimmer_test.cpp).
+ *   - AdapterTrimmer (src/adaptertrimmer.cpp) includes Google Highway; compiled against the
+ *     scalar stand-in of oracle/standin/hwy it joins the harness, and searchAdapter, the end
+ *     trims and findMiddleAdapters are cross-checked in tests/test_adaptertrimmer_vs_ref.py;
+ *   - processSingleEnd as a whole, with adapter auto-detection, is compared with the whole
+ *     reference program (oracle/_ref/fastplong_ref) in tests/test_cli_vs_ref_binary_stub.py.
  */
 #ifndef FPL_ORACLE_H
 #define FPL_ORACLE_H

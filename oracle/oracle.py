@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes front end of oracle/liboracle.so (the C restatement of
-the reference hot path) and a line-protocol client for oracle/_ref/ref_harness (real reference
-objects).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
+the reference hot path), a line-protocol client for oracle/_ref/ref_harness (real reference
+objects) and the path of oracle/_ref/fastplong_ref (the whole reference program).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 """
 import ctypes as C
 import os
@@ -13,6 +13,7 @@ from fastplong_amd import abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 REF_HARNESS = os.path.join(HERE, "_ref", "ref_harness")
+REF_BIN = os.path.join(HERE, "_ref", "fastplong_ref")
 
 
 class OrcRead(C.Structure):
@@ -30,12 +31,13 @@ class OrcConfig(C.Structure):
 
 def build(force=False):
     """Compile the C restatement (and, when /root/reference is present, the real-reference
-    harness).  Building the checker is not using it."""
+    harness and the reference program).  Building the checker is not using it."""
     if force:
         subprocess.check_call(["make", "-s", "-C", HERE, "clean"])
     subprocess.check_call(["make", "-s", "-C", HERE, "all"])  # make tracks the header dependencies
     if os.path.isdir("/root/reference/src"):
-        subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+        jobs = "-j%d" % max(1, min(8, len(os.sched_getaffinity(0))))
+        subprocess.check_call(["make", "-s", jobs, "-C", HERE, "ref", "refbin"])
 
 
 _lib = None
@@ -255,6 +257,10 @@ def have_ref():
     return os.path.exists(REF_HARNESS)
 
 
+def have_ref_bin():
+    return os.path.exists(REF_BIN)
+
+
 class RefHarness:
     """Feeds command lines to oracle/_ref/ref_harness and returns its raw stdout."""
 
@@ -272,3 +278,48 @@ class RefHarness:
         p = subprocess.run([REF_HARNESS], input=("\n".join(lines) + "\n").encode("latin-1"),
                            stdout=subprocess.PIPE, check=True)
         return p.stdout.decode("latin-1")
+
+    # ---- AdapterTrimmer / Sequence, one process per batch: each takes a list of argument tuples and returns the answers
+    def search_adapter(self, cases):
+        """[(seq, adapter, ed_max, start, length, as_left, as_right)] -> [int]"""
+        lines = ["SA %.17g %d %d %d %d %s %s" % (ed, st, ln, int(l), int(r), self.s(q), self.s(a))
+                 for q, a, ed, st, ln, l, r in cases]
+        return [int(x) for x in self.run(lines).split("\n")[:len(cases)]] if cases else []
+
+    def _trims(self, op, cases):
+        out = self.run(["%s %.17g %d %s %s" % (op, ed, ext, self.s(q), self.s(a)) for q, a, ed, ext in cases]).split("\n")
+        res = []
+        for line in out[:len(cases)]:
+            left, ret, kl = line.split(" ")
+            res.append((left[1:].encode("latin-1"), int(ret), int(kl)))
+        return res
+
+    def trim_start(self, cases):
+        """[(seq, adapter, ed_max, ext)] -> [(read_left bytes, returned, key_len)]"""
+        return self._trims("TSS", cases) if cases else []
+
+    def trim_end(self, cases):
+        return self._trims("TSE", cases) if cases else []
+
+    def find_middle(self, cases):
+        """[(seq, start_adapter, end_adapter, ed_max, ext)] -> [(found, start, len)]"""
+        if not cases:
+            return []
+        out = self.run(["FM %.17g %d %s %s %s" % (ed, ext, self.s(q), self.s(sa), self.s(ea))
+                        for q, sa, ea, ed, ext in cases]).split("\n")
+        return [(x[0] == "1", int(x[1]), int(x[2])) for x in (l.split(" ") for l in out[:len(cases)])]
+
+    def trim_multi(self, cases):
+        """[(seq, [adapters], ed_max, ext)] -> [(read_left bytes, returned)]"""
+        if not cases:
+            return []
+        out = self.run([" ".join(["TMS %.17g %d %s" % (ed, ext, self.s(q))] + [self.s(a) for a in ads])
+                        for q, ads, ed, ext in cases]).split("\n")
+        return [(l.split(" ")[0][1:].encode("latin-1"), int(l.split(" ")[1])) for l in out[:len(cases)]]
+
+    def reverse_complement(self, seqs):
+        """[bytes] -> [bytes], any byte values"""
+        if not seqs:
+            return []
+        out = self.run(["RCX =" + bytes(x).hex() for x in seqs]).split("\n")
+        return [bytes.fromhex(l[1:]) for l in out[:len(seqs)]]

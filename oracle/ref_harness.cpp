@@ -5,8 +5,9 @@
  * /root/reference/src by oracle/Makefile into oracle/_ref/).  It contains no algorithm of its
  * own: every answer it prints comes out of reference code.  Linked reference files:
  * editdistance, filter, polyx, stats, filterresult, read, options, fastareader, jsonreporter,
- * htmlreporter, writer, threadconfig (+ the system's libdeflate.so.0, which Writer calls for .gz names).  NOT linked (they include Google Highway / ISA-L headers the image lacks):
- * adaptertrimmer, sequence, fastqreader, seprocessor, evaluator, main.
+ * htmlreporter, writer, threadconfig, adaptertrimmer, sequence (+ the system's libdeflate.so.0, which Writer calls for .gz
+ * names).  adaptertrimmer and sequence include Google Highway: they are compiled against the scalar stand-in of
+ * oracle/standin/hwy.  The whole program (fastqreader, seprocessor, evaluator, main too) is oracle/_ref/fastplong_ref.
  *
  * Protocol (stdin, one command per line, fields separated by one space, strings carry a
  * leading '=' so that the empty string is "="):
@@ -25,6 +26,14 @@
  *               | J_PXT base len | J_END =path   -> Stats/FilterResult/JsonReporter::report
  *               | J_ENDH lf maxlen =json =html =title words...  -> the same plus calcLengthHistogram and
  *                 HtmlReporter::report (lf / maxlen = Options::lengthFilter.enabled / .maxLength)
+ *   SA ed start len left right =seq =adapter    -> AdapterTrimmer::searchAdapter (all six arguments)
+ *   TSS ed ext =seq =adapter / TSE ...          -> AdapterTrimmer::trimBySequenceStart / trimBySequenceEnd:
+ *                                                  "=read_left returned key_len" (key_len: the length of the key handed to
+ *                                                  FilterResult::addAdapterTrimmed, 0 when none, read back through
+ *                                                  FilterResult::reportAdapterJson)
+ *   FM ed ext =seq =start_adapter =end_adapter  -> AdapterTrimmer::findMiddleAdapters: "found start len"
+ *   TMS ed ext =seq =adapter...                 -> AdapterTrimmer::trimByMultiSequences: "=read_left returned"
+ *   RCX hex                                     -> Sequence::reverseComplement on any bytes (hex in, hex out; "=" for empty)
  *   FA =path                                    -> FastaReader::readAll: the contig count, then "=hex(header) =hex(sequence)"
  *                                                  per contig in map order
  *   --split / --split_by_lines block (real ThreadConfig + Writer objects, one per worker, as
@@ -35,8 +44,12 @@
  *                       prints canBeStopped() afterwards
  *               S_END   -> the ThreadConfig destructors (writeEmptyFilesForSplitting, writers flushed and closed)
  */
+#include <unistd.h>
+
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <mutex>
@@ -44,6 +57,7 @@
 #include <string>
 #include <vector>
 
+#include "adaptertrimmer.h"
 #include "editdistance.h"
 #include "fastareader.h"
 #include "filter.h"
@@ -53,6 +67,7 @@
 #include "options.h"
 #include "polyx.h"
 #include "read.h"
+#include "sequence.h"
 #include "stats.h"
 #include "threadconfig.h"
 
@@ -83,6 +98,41 @@ static string hex_of(const string& s) { /* (headers and sequences may hold any b
     return o;
 }
 static string str(const string& tok) { return tok.empty() ? string() : tok.substr(1); }
+static string unhex(const string& h) {
+    string o;
+    for (size_t i = 0; i + 1 < h.size(); i += 2) o += (char)strtol(h.substr(i, 2).c_str(), NULL, 16);
+    return o;
+}
+
+/* the one key a single trim handed to FilterResult::addAdapterTrimmed ("" for none): the counts map is private, so it is
+   read back from the reference's own JSON section ("read_adapter_counts": {"KEY":1}) */
+static string trimmed_key(FilterResult& fr) {
+    static string path;
+    if (path.empty()) {
+        char tmpl[] = "/tmp/ref_harness_keyXXXXXX";
+        int fd = mkstemp(tmpl);
+        if (fd < 0) {
+            perror("mkstemp");
+            exit(1);
+        }
+        close(fd);
+        path = tmpl;
+    }
+    {
+        ofstream ofs(path.c_str());
+        fr.reportAdapterJson(ofs, "");
+    }
+    ifstream ifs(path.c_str());
+    string text((istreambuf_iterator<char>(ifs)), istreambuf_iterator<char>());
+    unlink(path.c_str());
+    const string tag = "\"read_adapter_counts\": {";
+    size_t a = text.find(tag);
+    if (a == string::npos) return "";
+    a += tag.size();
+    if (text[a] != '"') return "";
+    size_t b = text.find('"', a + 1);
+    return text.substr(a + 1, b - a - 1);
+}
 
 struct JsonJob {
     Options opt;
@@ -215,6 +265,38 @@ int main() {
             string s;
             r.appendToStringWithTag(&s, FAILED_TYPES[atoi(t[1].c_str())]);
             cout << s.size() << "\n" << s;
+        } else if (op == "SA") {
+            string seq = str(t[6]), ad = str(t[7]);
+            cout << AdapterTrimmer::searchAdapter(&seq, ad, atof(t[1].c_str()), atoi(t[2].c_str()), atoi(t[3].c_str()),
+                                                  atoi(t[4].c_str()) != 0, atoi(t[5].c_str()) != 0)
+                 << "\n";
+        } else if (op == "TSS" || op == "TSE") {
+            Options opt;
+            FilterResult fr(&opt);
+            Read r("@n", str(t[3]).c_str(), "+", string(str(t[3]).size(), 'I').c_str());
+            string ad = str(t[4]);
+            const double ed = atof(t[1].c_str());
+            const int ext = atoi(t[2].c_str());
+            int ret = op == "TSS" ? AdapterTrimmer::trimBySequenceStart(&r, &fr, ad, ed, ext)
+                                  : AdapterTrimmer::trimBySequenceEnd(&r, &fr, ad, ed, ext);
+            cout << "=" << *r.mSeq << " " << ret << " " << trimmed_key(fr).size() << "\n";
+        } else if (op == "FM") {
+            Read r("@n", str(t[3]).c_str(), "+", string(str(t[3]).size(), 'I').c_str());
+            string sa = str(t[4]), ea = str(t[5]);
+            int start = -1, len = 0;
+            bool hit = AdapterTrimmer::findMiddleAdapters(&r, sa, ea, start, len, atof(t[1].c_str()), atoi(t[2].c_str()));
+            cout << (hit ? 1 : 0) << " " << start << " " << len << "\n";
+        } else if (op == "TMS") {
+            Options opt;
+            FilterResult fr(&opt);
+            Read r("@n", str(t[3]).c_str(), "+", string(str(t[3]).size(), 'I').c_str());
+            vector<string> ads;
+            for (size_t i = 4; i < t.size(); i++) ads.push_back(str(t[i]));
+            int ret = AdapterTrimmer::trimByMultiSequences(&r, &fr, ads, atof(t[1].c_str()), atoi(t[2].c_str()));
+            cout << "=" << *r.mSeq << " " << ret << "\n";
+        } else if (op == "RCX") {
+            string in = unhex(str(t[1]));
+            cout << "=" << hex_of(Sequence::reverseComplement(&in)) << "\n";
         } else if (op == "FA") { /* FastaReader::readAll, src/fastareader.cpp:91-101 */
             FastaReader reader(str(t[1]));
             reader.readAll();
