@@ -20,6 +20,7 @@
 
 #include "pipeline.h"
 #include "text_parse.h"
+#include "gz_emit.h"
 #include "bam_decode.h"
 
 using namespace fpl;
@@ -112,6 +113,25 @@ struct fpl_ctx {
         u32 h_line_cap = 0;
         uint64_t text_bytes = 0;
         hipEvent_t ev_parsed = nullptr;
+        /* a GZIP batch (fpl_set_text_gzip; csrc/gz_emit.h): a text batch whose passing reads also come back as a gzip member.  The
+           layout is enqueued behind the per-read kernels (text_continue); everything behind it is sized by what the layout
+           found and enqueued by fpl_wait_text_gz */
+        bool gz = false;
+        u32 gz_rec_cap = 0, gz_blk_cap = 0; /* entries d_rec_off / the d_gz_blk_* arrays hold */
+        u64* d_rec_off = nullptr;
+        u64* d_gz_blk_start = nullptr;
+        u64* d_gz_blk_off = nullptr;
+        u32* d_gz_blk_size = nullptr;
+        u32* d_gz_blk_crc = nullptr;
+        GzHeader* d_gz_hdr = nullptr;
+        GzHeader* h_gz_hdr = nullptr; /* pinned */
+        u8* d_gz_comp = nullptr;      /* the composed text */
+        u8* d_gz_tmp = nullptr;       /* every deflate block in a slot of its own */
+        u8* d_gz_out = nullptr;       /* the member */
+        uint64_t gz_comp_cap = 0, gz_out_cap = 0;
+        u8* h_gz = nullptr; /* pinned */
+        uint64_t h_gz_cap = 0;
+        hipEvent_t ev_gz = nullptr;
         /* a BAM batch (fpl_process_bam_async): the inflated record bytes and where every record starts; a CSR batch otherwise */
         u8* d_bam = nullptr;
         uint64_t bam_cap = 0;
@@ -131,6 +151,8 @@ struct fpl_ctx {
     int ev_calls = 0; /* batches recorded since fpl_enable_timing() */
     bool ev_ready = false; /* the whole event ring exists */
     uint64_t forms[6] = {0, 0, 0, 0, 0, 0}; /* fpl_get_batch_forms */
+    bool text_gzip = false;    /* fpl_set_text_gzip */
+    uint64_t gz_batches = 0;   /* fpl_get_gzip_batches */
     std::string err;
 };
 
@@ -240,6 +262,7 @@ int fpl_create(fpl_ctx** out, const fpl_options* opt, const char* start_adapter,
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_kern, hipEventDisableTiming));
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_parsed, hipEventDisableTiming));
+            FPL_HIP(hipEventCreateWithFlags(&sl.ev_gz, hipEventDisableTiming));
         }
         DevConfig cfg;
         build_config(&cfg, opt, start_len, end_len, n_fasta);
@@ -293,12 +316,17 @@ void fpl_destroy(fpl_ctx* ctx) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& sl : ctx->slot) {
-        void* sp[] = {sl.d_seq, sl.d_qual, sl.d_off, sl.d_results, sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len, sl.d_hdr, sl.d_bam, sl.d_rec};
+        void* sp[] = {sl.d_seq, sl.d_qual, sl.d_off, sl.d_results, sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len, sl.d_hdr, sl.d_bam, sl.d_rec,
+                      sl.d_rec_off, sl.d_gz_blk_start, sl.d_gz_blk_off, sl.d_gz_blk_size, sl.d_gz_blk_crc, sl.d_gz_hdr, sl.d_gz_comp,
+                      sl.d_gz_tmp, sl.d_gz_out};
         for (void* p : sp)
             if (p) (void)hipFree(p);
         if (sl.h_results) (void)hipHostFree(sl.h_results);
         if (sl.h_hdr) (void)hipHostFree(sl.h_hdr);
         if (sl.h_line) (void)hipHostFree(sl.h_line);
+        if (sl.h_gz_hdr) (void)hipHostFree(sl.h_gz_hdr);
+        if (sl.h_gz) (void)hipHostFree(sl.h_gz);
+        if (sl.ev_gz) (void)hipEventDestroy(sl.ev_gz);
         if (sl.ev_parsed) (void)hipEventDestroy(sl.ev_parsed);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
         if (sl.ev_kern) (void)hipEventDestroy(sl.ev_kern);
@@ -580,9 +608,16 @@ int fpl_get_batch_forms(const fpl_ctx* ctx, uint64_t out[6]) {
     return FPL_OK;
 }
 
+int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    *out = ctx->gz_batches;
+    return FPL_OK;
+}
+
 int fpl_reset_counters(fpl_ctx* ctx) {
     if (!ctx) return FPL_ERR_ARG;
     for (int i = 0; i < 6; i++) ctx->forms[i] = 0;
+    ctx->gz_batches = 0;
     FPL_HIP(hipSetDevice(ctx->device));
     FPL_HIP(hipDeviceSynchronize());
     FPL_HIP(hipMemset(ctx->d_counters, 0, fpl_counters_len(ctx) * sizeof(long long)));
@@ -929,6 +964,119 @@ static int ensure_text_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint64_t n_bytes) {
     return FPL_OK;
 }
 
+/* ---- gzip members of a text batch (ABI v9): csrc/gz_emit.h ---- */
+static int gz_grow(fpl_ctx* ctx, void** p, uint64_t& cap, uint64_t want) { /* bytes; 25 % headroom; a grow waits for the device */
+    if (want <= cap && *p) return FPL_OK;
+    FPL_HIP(hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    cap = 0;
+    const uint64_t c = want + want / 4 + 4096;
+    FPL_HIP(hipMalloc(p, c));
+    cap = c;
+    return FPL_OK;
+}
+/* behind the per-read kernels of the batch, on their stream: where every record's output and every deflate block starts */
+static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
+    if (!sl.d_gz_hdr) {
+        FPL_HIP(hipMalloc((void**)&sl.d_gz_hdr, sizeof(GzHeader)));
+        FPL_HIP(hipHostMalloc((void**)&sl.h_gz_hdr, sizeof(GzHeader), hipHostMallocDefault));
+    }
+    const uint64_t blk_want = gz_blocks_bound(sl.text_bytes, n) + 1;
+    if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
+    if ((uint64_t)n + 1 > sl.gz_rec_cap || !sl.d_rec_off) {
+        uint64_t cap = 0;
+        sl.gz_rec_cap = 0;
+        const int r = gz_grow(ctx, (void**)&sl.d_rec_off, cap, sizeof(u64) * ((uint64_t)n + 1));
+        if (r != FPL_OK) return r;
+        sl.gz_rec_cap = (u32)std::min<uint64_t>(cap / sizeof(u64), 0xFFFFFFFFull);
+    }
+    if (blk_want > sl.gz_blk_cap || !sl.d_gz_blk_start) {
+        FPL_HIP(hipDeviceSynchronize());
+        void* old[] = {sl.d_gz_blk_start, sl.d_gz_blk_off, sl.d_gz_blk_size, sl.d_gz_blk_crc};
+        for (void* p : old)
+            if (p) (void)hipFree(p);
+        sl.d_gz_blk_start = sl.d_gz_blk_off = nullptr;
+        sl.d_gz_blk_size = sl.d_gz_blk_crc = nullptr;
+        sl.gz_blk_cap = 0;
+        const uint64_t cap = std::min<uint64_t>(blk_want + blk_want / 4 + 64, 0xFFFFFFF0ull);
+        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_start, sizeof(uint64_t) * cap));
+        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_off, sizeof(uint64_t) * cap));
+        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_size, sizeof(u32) * cap));
+        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_crc, sizeof(u32) * cap));
+        sl.gz_blk_cap = (u32)cap;
+    }
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
+                       (const fpl_read_result*)sl.d_results, n, sl.d_rec_off, sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
+    FPL_HIP(hipGetLastError());
+    FPL_HIP(hipMemcpyAsync(sl.h_gz_hdr, sl.d_gz_hdr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
+    FPL_HIP(hipEventRecord(sl.ev_gz, st));
+    return FPL_OK;
+}
+/* the layout is in: buffers of the sizes it found, the other kernels, the member's way back.  *gz / *gz_len: see the header */
+static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t* gz_len) {
+    FPL_HIP(hipEventSynchronize(sl.ev_gz));
+    const GzHeader h = *sl.h_gz_hdr;
+    if (h.status) {
+        ctx->err = "gzip layout: more deflate blocks than the bound allows";
+        return FPL_ERR_STATE;
+    }
+    if (h.total == 0) return FPL_OK;
+    const u32 n = sl.n_reads;
+    const uint64_t out_want = GZ_MEMBER_EXTRA + h.total + (uint64_t)GZ_SLACK * h.n_blocks;
+    int r = gz_grow(ctx, (void**)&sl.d_gz_comp, sl.gz_comp_cap, h.total + 16);
+    if (r != FPL_OK) return r;
+    if (out_want + 16 > sl.gz_out_cap || !sl.d_gz_out) {
+        uint64_t c1 = 0, c2 = 0;
+        if (sl.d_gz_tmp) {
+            FPL_HIP(hipDeviceSynchronize());
+            (void)hipFree(sl.d_gz_tmp);
+            sl.d_gz_tmp = nullptr;
+        }
+        r = gz_grow(ctx, (void**)&sl.d_gz_tmp, c1, out_want + 16);
+        if (r != FPL_OK) return r;
+        r = gz_grow(ctx, (void**)&sl.d_gz_out, c2, out_want + 16);
+        if (r != FPL_OK) return r;
+        sl.gz_out_cap = std::min(c1, c2);
+    }
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
+                       (const fpl_read_result*)sl.d_results, n, (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
+    const u32 grid = std::max<u32>(1u, std::min<u32>(h.n_blocks, 8u * ctx->n_cu));
+    hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)sl.d_gz_comp, (const u64*)sl.d_gz_blk_start,
+                       (const GzHeader*)sl.d_gz_hdr, sl.d_gz_tmp, sl.d_gz_blk_size, sl.d_gz_blk_crc);
+    hipLaunchKernelGGL(k_gz_finish, dim3(1), dim3(1024), 0, st, (const u32*)sl.d_gz_blk_size, (const u32*)sl.d_gz_blk_crc, (u64*)sl.d_gz_blk_off,
+                       sl.d_gz_hdr, sl.d_gz_out, (u64)out_want);
+    hipLaunchKernelGGL(k_gz_compact, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)sl.d_gz_tmp, (const u64*)sl.d_gz_blk_start,
+                       (const u32*)sl.d_gz_blk_size, (const u64*)sl.d_gz_blk_off, (const GzHeader*)sl.d_gz_hdr, sl.d_gz_out, (u64)out_want);
+    FPL_HIP(hipGetLastError());
+    FPL_HIP(hipMemcpyAsync(sl.h_gz_hdr, sl.d_gz_hdr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
+    FPL_HIP(hipEventRecord(sl.ev_gz, st));
+    if (out_want > sl.h_gz_cap) { /* (beside the kernels) */
+        if (sl.h_gz) (void)hipHostFree(sl.h_gz);
+        sl.h_gz = nullptr;
+        sl.h_gz_cap = 0;
+        const uint64_t cap = out_want + out_want / 4 + 4096;
+        FPL_HIP(hipHostMalloc((void**)&sl.h_gz, cap, hipHostMallocDefault));
+        sl.h_gz_cap = cap;
+    }
+    FPL_HIP(hipEventSynchronize(sl.ev_gz));
+    const GzHeader h2 = *sl.h_gz_hdr;
+    if (h2.status || h2.gz_len == 0 || h2.gz_len > out_want) {
+        ctx->err = "gzip member: the kernels report a size outside the bound";
+        return FPL_ERR_STATE;
+    }
+    /* (the kernels are done: the member goes back on the copy stream, beside the next batch's kernels) */
+    FPL_HIP(hipMemcpyAsync(sl.h_gz, sl.d_gz_out, h2.gz_len, hipMemcpyDeviceToHost, ctx->s_d2h));
+    FPL_HIP(hipEventRecord(sl.ev_gz, ctx->s_d2h));
+    FPL_HIP(hipEventSynchronize(sl.ev_gz));
+    *gz = sl.h_gz;
+    *gz_len = h2.gz_len;
+    ctx->gz_batches++;
+    return FPL_OK;
+}
+
 /* stage 2 of a text batch: the header is in -- enqueue the per-read kernels and the way back of the records and line starts */
 /* (called by fpl_wait_text only: a submission never waits for a parse, so the next chunk's copy goes out behind this one's at
    once -- no round trip to the host between two chunks on the link -- and a batch that has only been peeked at is in no counter) */
@@ -963,6 +1111,7 @@ static int text_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl) {
     FPL_HIP(hipMemcpyAsync(sl.h_line, sl.d_line, sizeof(u32) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->s_d2h));
     FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
     sl.n_reads = n;
+    if (sl.gz) return gz_layout(ctx, sl, n);
     return FPL_OK;
 }
 int fpl_process_text_async(fpl_ctx* ctx, const uint8_t* text, uint64_t n_bytes) {
@@ -974,6 +1123,7 @@ int fpl_process_text_async(fpl_ctx* ctx, const uint8_t* text, uint64_t n_bytes) 
     int r = FPL_OK;
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = 1;
+    sl.gz = ctx->text_gzip;
     sl.stage = 2;
     sl.cancelled = false;
     sl.n_reads = 0;
@@ -1082,7 +1232,26 @@ int fpl_cancel_text(fpl_ctx* ctx) {
     return FPL_OK;
 }
 
+int fpl_set_text_gzip(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    ctx->text_gzip = on != 0;
+    return FPL_OK;
+}
+
+static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
+                     const uint8_t** gz, uint64_t* gz_len);
 int fpl_wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts) {
+    return wait_text(ctx, out, results, line_starts, nullptr, nullptr);
+}
+int fpl_wait_text_gz(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
+                     const uint8_t** gz, uint64_t* gz_len) {
+    if (!gz || !gz_len) return FPL_ERR_ARG;
+    *gz = nullptr;
+    *gz_len = 0;
+    return wait_text(ctx, out, results, line_starts, gz, gz_len);
+}
+static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
+                     const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;
     if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
     fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
@@ -1105,6 +1274,10 @@ int fpl_wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** re
     if (sl.rc != FPL_OK) return sl.rc;
     text_info(sl, out);
     if (out->status != FPL_TEXT_OK || sl.n_reads == 0) return FPL_OK;
+    if (gz && sl.gz) {
+        const int r = gz_emit(ctx, sl, gz, gz_len);
+        if (r != FPL_OK) return r;
+    }
     FPL_HIP(hipEventSynchronize(sl.ev_done));
     if (results) *results = sl.h_results;
     if (line_starts) *line_starts = sl.h_line;

@@ -1,0 +1,672 @@
+/*
+ * gz_emit.h -- the passing reads of a TEXT batch as gzip members, composed and Huffman-coded ON THE DEVICE
+ * (fpl_set_text_gzip / fpl_wait_text_gz, include/fastplong_amd.h).
+ *
+ * Input: the chunk's text, where its lines start and end (text_parse.h: line[], nl_pos[]) and the per-read records.  Output: one
+ * gzip member (RFC 1952) whose inflation is exactly what fplh::format_batch (host/fastq.cpp, format_range without a fragment
+ * list) appends for that batch; nothing at all when no read passed.  Long-read FASTQ has next to nothing for LZ77 to find, so the
+ * deflate stream holds literals only: the gain is the entropy code, and blocks are cut so that bases and qualities -- which share
+ * byte values -- mostly get tables of their own.
+ *
+ *   k_gz_layout   one block, lane = read: output length of every record, exclusive prefix sums, and where deflate blocks START:
+ *                 at every multiple of GZ_B of the output, and for a fragment whose bases line has at least GZ_L bytes at its
+ *                 name line and at its '+' line (so [name + bases] and ['+' + qualities] are blocks of their own; what follows a
+ *                 long fragment joins its quality block up to the next multiple of GZ_B).  No block is longer than GZ_B.
+ *   k_gz_compose  a wave per record: the pieces to their offsets, 16 bytes a lane where the lengths allow
+ *   k_gz_block    a workgroup per deflate block: the bytes into LDS, a 257-bin histogram, the raw CRC of the block, code lengths
+ *                 limited to 15 bits (Moffat-Katajainen on the sorted counts, then a Kraft repair on the counts per length),
+ *                 canonical codes, the dynamic header (code-length code limited to 7 bits, zero runs as symbols 17 / 18, one
+ *                 distance code), and the pack: every thread owns GZ_STRETCH symbols, a prefix sum of their bits says where its
+ *                 codes go, words inside its range are stored, the two at its ends merged with LDS atomics.  A block ends with an
+ *                 empty stored block that byte-aligns it (what pigz does), so blocks are independent; a block that would not get
+ *                 smaller is one stored block.  The result goes to a slot of its own: at most its length + GZ_SLACK bytes.
+ *   k_gz_finish   one block: prefix sums of the blocks' sizes, the member's CRC-32 folded from the blocks' (every block's raw
+ *                 remainder times x^(8 * bytes behind it) mod P: no order between blocks), the gzip header, the final empty
+ *                 block and the trailer
+ *   k_gz_compact  a workgroup per deflate block: its bytes to their place in the member
+ *
+ * Worst case: gz_len <= GZ_MEMBER_EXTRA + total + GZ_SLACK * n_blocks, n_blocks <= total / GZ_B + 1 + 2 * (long fragments).
+ */
+#ifndef FPL_GZ_EMIT_H
+#define FPL_GZ_EMIT_H
+
+#include "../../include/fastplong_amd.h"
+#include "dev_prims.h"
+
+namespace fpl {
+
+typedef uint16_t u16;
+constexpr u32 GZ_B = 16384;  /* most bytes of a deflate block (docs/kernels.md: the table behind GZ_B and GZ_L) */
+constexpr u32 GZ_L = 1024;   /* a bases line of at least this many bytes starts blocks of its own */
+constexpr int GZ_THREADS = 256;
+constexpr u32 GZ_STRETCH = GZ_B / GZ_THREADS; /* symbols a thread packs */
+constexpr u32 GZ_SLACK = 5;                   /* a stored block's header: the most a block grows by */
+constexpr u32 GZ_MEMBER_EXTRA = 10 + 5 + 8;   /* gzip header, final empty block, CRC-32 + ISIZE */
+constexpr u32 GZ_CRC_POLY = 0xEDB88320u;
+constexpr int GZ_NSYM = 257; /* 256 literals + end-of-block */
+
+struct GzHeader {
+    u64 total;    /* bytes of the composed text */
+    u64 gz_len;   /* bytes of the member (0 when total is 0) */
+    u32 n_blocks; /* deflate blocks with data */
+    u32 status;   /* bit 0: more blocks than the caller's arrays hold (nothing usable) */
+    u32 crc;      /* CRC-32 of the composed text */
+    u32 pad;
+};
+
+/* most deflate blocks a chunk of text_bytes bytes and n_rec records can be cut into (both fragments of a split read repeat the
+   name and the '+' line, and each may start two blocks) */
+inline u64 gz_total_bound(u64 text_bytes, u64 n_rec) { return 2 * text_bytes + 46 * n_rec; }
+inline u64 gz_blocks_bound(u64 text_bytes, u64 n_rec) { return gz_total_bound(text_bytes, n_rec) / GZ_B + 2 + 4 * n_rec; }
+
+/* ---- CRC-32 arithmetic (reflected: bit 31 is x^0) ---- */
+__device__ __forceinline__ u32 gz_mulmod(u32 a, u32 b) { /* a * b mod P */
+    u32 p = 0;
+    for (int i = 0; i < 32; i++) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b >> 1) ^ ((b & 1u) ? GZ_CRC_POLY : 0u);
+    }
+    return p;
+}
+__device__ __forceinline__ u32 gz_xpow8(u64 n) { /* x^(8 n) mod P */
+    u32 r = 0x80000000u, sq = 0x00800000u; /* x^0, x^8 */
+    while (n) {
+        if (n & 1ull) r = gz_mulmod(r, sq);
+        sq = gz_mulmod(sq, sq);
+        n >>= 1;
+    }
+    return r;
+}
+__device__ __forceinline__ u32 gz_crc_table_entry(u32 i) {
+    u32 c = i;
+    for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? GZ_CRC_POLY : 0u);
+    return c;
+}
+
+/* ---- what a read writes ---- */
+struct GzRec {
+    u32 name_at, name_len, strand_at, strand_len, seq_at, qual_at;
+};
+__device__ __forceinline__ u32 gz_line_len(const u8* __restrict__ text, u32 at, u32 nl) {
+    u32 e = nl; /* the '\n' */
+    if (e > at && text[e - 1] == '\r') e--;
+    return e - at;
+}
+__device__ __forceinline__ GzRec gz_rec(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos, u32 r) {
+    GzRec g;
+    g.name_at = line[4 * (size_t)r];
+    g.seq_at = line[4 * (size_t)r + 1];
+    g.strand_at = line[4 * (size_t)r + 2];
+    g.qual_at = line[4 * (size_t)r + 3];
+    g.name_len = gz_line_len(text, g.name_at, nl_pos[4 * (size_t)r]);
+    g.strand_len = gz_line_len(text, g.strand_at, nl_pos[4 * (size_t)r + 2]);
+    return g;
+}
+__device__ __forceinline__ u32 gz_prefix_len(u32 kind, u32 name_len) { /* "split-by-adapter-left-" / "split-by-adapter-right-" */
+    return name_len == 0 ? 0u : (kind == 1 ? 22u : (kind == 2 ? 23u : 0u));
+}
+/* bytes of fragment f's name + bases lines (a) and of its '+' + quality lines (b) */
+__device__ __forceinline__ void gz_frag_len(const GzRec& g, const fpl_read_result& r, int f, u64& a, u64& b) {
+    a = (u64)g.name_len + gz_prefix_len(r.kind[f], g.name_len) + 1 + (u64)r.frag_len[f] + 1;
+    b = (u64)g.strand_len + 1 + (u64)r.frag_len[f] + 1;
+}
+/* the block starts inside [s, e): s itself when forced or on a multiple of GZ_B, and every multiple of GZ_B behind it */
+template <class F>
+__device__ __forceinline__ void gz_cuts(u64 s, u64 e, bool force, F&& emit) {
+    if (e <= s) return;
+    if (force || s % GZ_B == 0) emit(s);
+    for (u64 m = (s / GZ_B + 1) * GZ_B; m < e; m += GZ_B) emit(m);
+}
+template <class F>
+__device__ __forceinline__ void gz_read_cuts(const GzRec& g, const fpl_read_result& r, u64 o, F&& emit) {
+    if (r.dropped) return;
+    for (int f = 0; f < r.n_frag && f < 2; f++) {
+        if (r.code[f] != FPL_PASS_FILTER) continue;
+        u64 a, b;
+        gz_frag_len(g, r, f, a, b);
+        if ((u64)r.frag_len[f] + 1 >= GZ_L) {
+            gz_cuts(o, o + a, true, emit);
+            gz_cuts(o + a, o + a + b, true, emit);
+        } else {
+            gz_cuts(o, o + a + b, false, emit);
+        }
+        o += a + b;
+    }
+}
+
+__device__ __forceinline__ u64 gz_scan_incl_u64(u64 v) {
+    u64 incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 up = shfl_u64(incl, lane_id() - d < 0 ? lane_id() : lane_id() - d);
+        if (lane_id() >= d) incl += up;
+    }
+    return incl;
+}
+
+/* one block.  rec_off[r] = where record r's output starts (n_rec + 1 entries), blk_start[b] = where deflate block b starts
+   (n_blocks + 1 entries, the last one the total) */
+__global__ void __launch_bounds__(1024)
+k_gz_layout(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+            const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap,
+            GzHeader* __restrict__ hdr) {
+    __shared__ u64 wsum[16];
+    __shared__ u64 carry_len, carry_blk;
+    if (threadIdx.x == 0) carry_len = 0, carry_blk = 0;
+    __syncthreads();
+    for (u32 base = 0; base < n_rec; base += 1024) { /* block-uniform */
+        const u32 i = base + threadIdx.x;
+        GzRec g = {};
+        fpl_read_result r = {};
+        u64 len = 0;
+        if (i < n_rec) {
+            g = gz_rec(text, line, nl_pos, i);
+            r = res[i];
+            if (!r.dropped)
+                for (int f = 0; f < r.n_frag && f < 2; f++)
+                    if (r.code[f] == FPL_PASS_FILTER) {
+                        u64 a, b;
+                        gz_frag_len(g, r, f, a, b);
+                        len += a + b;
+                    }
+        }
+        u64 incl = gz_scan_incl_u64(len);
+        if (lane_id() == 63) wsum[wave_in_block()] = incl;
+        __syncthreads();
+        u64 o = carry_len + incl - len;
+        for (int k = 0; k < wave_in_block(); k++) o += wsum[k];
+        if (i < n_rec) rec_off[i] = o;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry_len = o + len;
+        /* the blocks that start inside this record */
+        u64 cnt = 0;
+        if (i < n_rec) gz_read_cuts(g, r, o, [&](u64) { cnt++; });
+        incl = gz_scan_incl_u64(cnt);
+        if (lane_id() == 63) wsum[wave_in_block()] = incl;
+        __syncthreads();
+        u64 k0 = carry_blk + incl - cnt;
+        for (int k = 0; k < wave_in_block(); k++) k0 += wsum[k];
+        if (i < n_rec) {
+            u64 k = k0;
+            gz_read_cuts(g, r, o, [&](u64 p) {
+                if (k < blk_cap) blk_start[k] = p;
+                k++;
+            });
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) carry_blk = k0 + cnt;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        rec_off[n_rec] = carry_len;
+        hdr->total = carry_len;
+        hdr->gz_len = 0;
+        hdr->crc = 0;
+        hdr->pad = 0;
+        if (carry_blk < blk_cap) {
+            blk_start[carry_blk] = carry_len;
+            hdr->n_blocks = (u32)carry_blk;
+            hdr->status = 0;
+        } else {
+            hdr->n_blocks = 0;
+            hdr->status = 1;
+        }
+    }
+}
+
+/* len bytes, the wave together; neither side is aligned */
+__device__ __forceinline__ void gz_wave_copy(u8* __restrict__ dst, const u8* __restrict__ src, u32 len) {
+    const u32 lane = (u32)lane_id();
+    const u32 whole = len & ~15u;
+    for (u32 i = 16 * lane; i < whole; i += 16 * 64) {
+        u32x4 v;
+        __builtin_memcpy(&v, src + i, 16);
+        __builtin_memcpy(dst + i, &v, 16);
+    }
+    if (lane < (len & 15u)) dst[whole + lane] = src[whole + lane];
+}
+
+/* a wave per record; comp holds hdr->total bytes (the caller sized it after k_gz_layout: comp_cap is checked all the same) */
+__global__ void __launch_bounds__(256)
+k_gz_compose(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+             const fpl_read_result* __restrict__ res, u32 n_rec, const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const u32 lane = (u32)lane_id();
+    for (u32 i = wave; i < n_rec; i += n_waves) { /* wave-uniform */
+        const u64 o0 = rec_off[i], o1 = rec_off[i + 1];
+        if (o1 == o0 || o1 > comp_cap) continue;
+        const GzRec g = gz_rec(text, line, nl_pos, i);
+        const fpl_read_result r = res[i];
+        u8* d = comp + o0;
+        for (int f = 0; f < r.n_frag && f < 2; f++) {
+            if (r.code[f] != FPL_PASS_FILTER) continue;
+            const u32 pl = gz_prefix_len(r.kind[f], g.name_len);
+            const u32 fl = r.frag_len[f], fs = r.frag_start[f];
+            if (pl) {
+                if (lane == 0) d[0] = text[g.name_at];
+                if (lane < pl) {
+                    const char* pf = pl == 22 ? "split-by-adapter-left-" : "split-by-adapter-right-";
+                    d[1 + lane] = (u8)pf[lane];
+                }
+                gz_wave_copy(d + 1 + pl, text + g.name_at + 1, g.name_len - 1);
+            } else {
+                gz_wave_copy(d, text + g.name_at, g.name_len);
+            }
+            d += g.name_len + pl;
+            gz_wave_copy(d + 1, text + g.seq_at + fs, fl);
+            u8* d2 = d + 1 + fl + 1;
+            gz_wave_copy(d2, text + g.strand_at, g.strand_len);
+            u8* d3 = d2 + g.strand_len + 1;
+            gz_wave_copy(d3, text + g.qual_at + fs, fl);
+            if (lane == 0) {
+                d[0] = '\n';
+                d2[-1] = '\n';
+                d3[-1] = '\n';
+                d3[fl] = '\n';
+            }
+            d = d3 + fl + 1;
+        }
+    }
+}
+
+/* ---- code lengths: the whole workgroup; everything in LDS ---- */
+struct GzCodeScratch {
+    u32 key[GZ_NSYM + 3];  /* counts in ascending order, then the algorithm's work array */
+    u16 sym[GZ_NSYM + 3];  /* the symbol at each rank */
+    u32 cnt[17];           /* symbols per length */
+    u32 n;                 /* symbols in use */
+};
+/* len[s] for s < nsym: a prefix code of at most maxbits bits for the symbols whose freq is not 0 (complete when two or more are
+   in use; one symbol gets length 1).  Called by every thread of the workgroup. */
+__device__ inline void gz_code_lengths(const u32* freq, int nsym, int maxbits, u8* len, GzCodeScratch* S) {
+    const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
+    /* rank by (count, symbol): a counting sort, one or two symbols a thread */
+    for (int s = tid; s < nsym; s += nthr) {
+        const u32 f = freq[s];
+        u32 rank = 0, used = 0;
+        for (int t = 0; t < nsym; t++) {
+            const u32 ft = freq[t];
+            if (ft) {
+                used++;
+                if (f && (ft < f || (ft == f && t < s))) rank++;
+            }
+        }
+        len[s] = 0;
+        if (f) {
+            S->key[rank] = f;
+            S->sym[rank] = (u16)s;
+        }
+        if (s == 0) S->n = used;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int n = (int)S->n;
+        u32* A = S->key;
+        if (n == 1) {
+            A[0] = 1;
+        } else if (n >= 2) {
+            /* Moffat & Katajainen, "In-place calculation of minimum-redundancy codes": A[] ascending counts -> code lengths */
+            A[0] += A[1];
+            int root = 0, leaf = 2;
+            for (int next = 1; next < n - 1; next++) {
+                if (leaf >= n || A[root] < A[leaf]) {
+                    A[next] = A[root];
+                    A[root++] = (u32)next;
+                } else {
+                    A[next] = A[leaf++];
+                }
+                if (leaf >= n || (root < next && A[root] < A[leaf])) {
+                    A[next] += A[root];
+                    A[root++] = (u32)next;
+                } else {
+                    A[next] += A[leaf++];
+                }
+            }
+            A[n - 2] = 0;
+            for (int next = n - 3; next >= 0; next--) A[next] = A[A[next]] + 1;
+            int avbl = 1, used = 0, dpth = 0;
+            root = n - 2;
+            int next = n - 1;
+            while (avbl > 0) {
+                while (root >= 0 && (int)A[root] == dpth) {
+                    used++;
+                    root--;
+                }
+                while (avbl > used) {
+                    A[next--] = (u32)dpth;
+                    avbl--;
+                }
+                avbl = 2 * used;
+                dpth++;
+                used = 0;
+            }
+        }
+        /* counts per length, lengths above the limit folded into it, then the Kraft sum brought back to exactly 2^maxbits: every
+           step takes one code off the longest length and splits the deepest shorter one in two */
+        for (int l = 0; l <= 16; l++) S->cnt[l] = 0;
+        for (int k = 0; k < n; k++) S->cnt[min((int)A[k], maxbits)]++;
+        if (n >= 2) {
+            u32 total = 0;
+            for (int l = maxbits; l > 0; l--) total += S->cnt[l] << (maxbits - l);
+            while (total != (1u << maxbits)) {
+                S->cnt[maxbits]--;
+                for (int l = maxbits - 1; l > 0; l--)
+                    if (S->cnt[l]) {
+                        S->cnt[l]--;
+                        S->cnt[l + 1] += 2;
+                        break;
+                    }
+                total--;
+            }
+        }
+        /* the rarest symbols get the longest codes */
+        int k = 0;
+        for (int l = maxbits; l >= 1; l--)
+            for (u32 c = 0; c < S->cnt[l]; c++) len[S->sym[k++]] = (u8)l;
+    }
+    __syncthreads();
+}
+
+/* thread-private bit writer into a zeroed LDS word array that other threads write too */
+struct GzBits {
+    u32* w;
+    u32 pos;
+    __device__ __forceinline__ void put(u32 val, u32 nbits) { /* nbits <= 16 */
+        if (nbits == 0) return;
+        const u32 i = pos >> 5, s = pos & 31u;
+        atomicOr(&w[i], val << s);
+        if (s + nbits > 32) atomicOr(&w[i + 1], val >> (32 - s));
+        pos += nbits;
+    }
+};
+__device__ __forceinline__ u32 gz_rev(u32 code, u32 len) { return len ? brev32(code) >> (32 - len) : 0u; }
+
+constexpr u32 GZ_OUT_WORDS = (GZ_B + GZ_SLACK + 3) / 4 + 2;
+
+/* a workgroup per deflate block.  tmp: block b's bytes at blk_start[b] + GZ_SLACK * b, blk_size[b] of them;
+   blk_crc[b]: the block's share of the member's raw CRC remainder */
+__global__ void __launch_bounds__(GZ_THREADS)
+k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const GzHeader* __restrict__ hdr, u8* __restrict__ tmp,
+           u32* __restrict__ blk_size, u32* __restrict__ blk_crc) {
+    __shared__ u32 in_w[GZ_B / 4 + 4];
+    __shared__ u32 out_w[GZ_OUT_WORDS];
+    __shared__ u32 hist[GZ_NSYM + 3];
+    __shared__ u8 len[GZ_NSYM + 3];
+    __shared__ u16 code[GZ_NSYM + 3]; /* bit-reversed: as it goes into the stream */
+    __shared__ u32 crc_tab[256];
+    __shared__ GzCodeScratch scratch;
+    __shared__ u8 cl_sym[GZ_NSYM + 8], cl_extra[GZ_NSYM + 8];
+    __shared__ u32 cl_freq[19];
+    __shared__ u8 cl_len[19 + 1];
+    __shared__ u32 wsum[GZ_THREADS / 64];
+    __shared__ u32 n_hdr_bits, use_stored, out_size, n_cl;
+    const u32 tid = threadIdx.x;
+    u8* in = (u8*)in_w;
+    const u32 n_blocks = hdr->n_blocks;
+    const u64 total = hdr->total;
+    crc_tab[tid] = gz_crc_table_entry(tid);
+    /* x^(8 * GZ_STRETCH * (threads behind this one)): what this thread's stretch of a block is shifted by (the block's bytes are
+       taken as ENDING at the end of the last thread's stretch: zero bytes in front change no remainder) */
+    const u32 my_shift = gz_xpow8((u64)GZ_STRETCH * (GZ_THREADS - 1 - tid));
+    for (u32 b = blockIdx.x; b < n_blocks; b += gridDim.x) { /* block-uniform */
+        __syncthreads();
+        const u64 s0 = blk_start[b];
+        const u32 n = (u32)(blk_start[b + 1] - s0); /* 1 .. GZ_B */
+        const u8* src = comp + s0;
+        /* the bytes, coalesced */
+        for (u32 i = 16 * tid; i + 16 <= n; i += 16 * GZ_THREADS) {
+            u32x4 v;
+            __builtin_memcpy(&v, src + i, 16);
+            in_w[i / 4] = v.x, in_w[i / 4 + 1] = v.y, in_w[i / 4 + 2] = v.z, in_w[i / 4 + 3] = v.w;
+        }
+        if (tid < (n & 15u)) in[(n & ~15u) + tid] = src[(n & ~15u) + tid];
+        for (u32 i = tid; i < GZ_NSYM; i += GZ_THREADS) hist[i] = i == 256 ? 1u : 0u;
+        for (u32 i = tid; i < GZ_OUT_WORDS; i += GZ_THREADS) out_w[i] = 0;
+        __syncthreads();
+        /* histogram of this thread's symbols; CRC of its stretch of the end-aligned block */
+        const u32 a0 = min(n, tid * GZ_STRETCH), a1 = min(n, (tid + 1) * GZ_STRETCH);
+        for (u32 i = a0; i < a1; i++) atomicAdd(&hist[in[i]], 1u);
+        {
+            const u32 pad = GZ_B - n;
+            const u32 c0 = tid * GZ_STRETCH > pad ? tid * GZ_STRETCH - pad : 0u;
+            const u32 c1 = (tid + 1) * GZ_STRETCH > pad ? (tid + 1) * GZ_STRETCH - pad : 0u;
+            u32 c = 0;
+            for (u32 i = c0; i < c1; i++) c = crc_tab[(c ^ in[i]) & 0xFFu] ^ (c >> 8);
+            c = c ? gz_mulmod(c, my_shift) : 0u;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) c ^= shfl_xor_u32(c, d);
+            if (lane_id() == 0) wsum[wave_in_block()] = c;
+        }
+        __syncthreads();
+        if (tid == 64) { /* (beside thread 0's serial work below) */
+            u32 c = 0;
+            for (int k = 0; k < GZ_THREADS / 64; k++) c ^= wsum[k];
+            blk_crc[b] = gz_mulmod(c, gz_xpow8(total - (s0 + n)));
+        }
+        gz_code_lengths(hist, GZ_NSYM, 15, len, &scratch);
+        /* canonical codes: symbols of one length in symbol order */
+        if (tid == 0) {
+            u32 next = 0;
+            scratch.cnt[0] = 0;
+            for (int l = 1; l <= 15; l++) { /* cnt[l] := first code of length l */
+                const u32 c = scratch.cnt[l];
+                scratch.cnt[l] = next;
+                next = (next + c) << 1;
+            }
+        }
+        __syncthreads();
+        for (u32 s = tid; s < GZ_NSYM; s += GZ_THREADS) {
+            const u32 l = len[s];
+            u32 rank = 0;
+            for (u32 t = 0; t < s; t++) rank += len[t] == l;
+            code[s] = (u16)(l ? gz_rev(scratch.cnt[l] + rank, l) : 0u);
+        }
+        __syncthreads();
+        /* the header: run-length symbols over the 257 literal lengths and the one distance length (1) */
+        if (tid == 0) {
+            u32 m = 0;
+            for (int i = 0; i < 19; i++) cl_freq[i] = 0;
+            for (u32 i = 0; i < GZ_NSYM + 1;) {
+                const u32 v = i < GZ_NSYM ? len[i] : 1u;
+                if (v != 0) {
+                    cl_sym[m] = (u8)v, cl_extra[m] = 0, m++, i++;
+                    cl_freq[v]++;
+                    continue;
+                }
+                u32 run = 1;
+                while (i + run < GZ_NSYM && len[i + run] == 0) run++;
+                i += run;
+                while (run >= 11) {
+                    const u32 t = min(run, 138u);
+                    cl_sym[m] = 18, cl_extra[m] = (u8)(t - 11), m++;
+                    cl_freq[18]++;
+                    run -= t;
+                }
+                if (run >= 3) {
+                    cl_sym[m] = 17, cl_extra[m] = (u8)(run - 3), m++;
+                    cl_freq[17]++;
+                    run = 0;
+                }
+                for (; run; run--) {
+                    cl_sym[m] = 0, cl_extra[m] = 0, m++;
+                    cl_freq[0]++;
+                }
+            }
+            n_cl = m;
+        }
+        __syncthreads();
+        gz_code_lengths(cl_freq, 19, 7, cl_len, &scratch);
+        if (tid == 0) {
+            /* literal bits (end-of-block included) */
+            u32 body = 0;
+            for (u32 s = 0; s < GZ_NSYM; s++) body += hist[s] * len[s];
+            u32 first[8], next = 0, cl_code[19];
+            for (int l = 1; l <= 7; l++) {
+                first[l] = next;
+                next = (next + scratch.cnt[l]) << 1;
+            }
+            for (int s = 0; s < 19; s++) {
+                const u32 l = cl_len[s];
+                cl_code[s] = l ? gz_rev(first[l]++, l) : 0u;
+            }
+            const u8 order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+            u32 hclen = 19;
+            while (hclen > 4 && cl_len[order[hclen - 1]] == 0) hclen--;
+            GzBits bw = {out_w, 0};
+            bw.put(0, 1);  /* BFINAL */
+            bw.put(2, 2);  /* BTYPE: dynamic */
+            bw.put(0, 5);  /* HLIT: 257 codes */
+            bw.put(0, 5);  /* HDIST: 1 code */
+            bw.put(hclen - 4, 4);
+            for (u32 i = 0; i < hclen; i++) bw.put(cl_len[order[i]], 3);
+            const u32 m = n_cl;
+            for (u32 i = 0; i < m; i++) {
+                const u32 s = cl_sym[i];
+                bw.put(cl_code[s], cl_len[s]);
+                if (s == 17) bw.put(cl_extra[i], 3);
+                if (s == 18) bw.put(cl_extra[i], 7);
+            }
+            const u32 hdr_bits = bw.pos;
+            /* end of block sits in `body`; then the empty stored block: 3 header bits, up to the byte, 00 00 FF FF */
+            const u32 end_bits = hdr_bits + body + 3;
+            const u32 dyn_bytes = (end_bits + 7) / 8 + 4;
+            n_hdr_bits = hdr_bits;
+            use_stored = dyn_bytes >= n + GZ_SLACK;
+            out_size = use_stored ? n + GZ_SLACK : dyn_bytes;
+            if (!use_stored) {
+                bw.pos = hdr_bits + body - len[256];
+                bw.put(code[256], len[256]);
+                bw.pos = (end_bits + 7) / 8 * 8 + 16;
+                bw.put(0xFFFFu, 16);
+            }
+        }
+        __syncthreads();
+        u8* dst = tmp + s0 + (u64)GZ_SLACK * b;
+        const u32 size = out_size;
+        if (use_stored) {
+            if (tid == 0) {
+                dst[0] = 0;
+                dst[1] = (u8)(n & 0xFF), dst[2] = (u8)(n >> 8);
+                dst[3] = (u8)(~n & 0xFF), dst[4] = (u8)((~n >> 8) & 0xFF);
+            }
+            for (u32 i = tid; i < n; i += GZ_THREADS) dst[GZ_SLACK + i] = in[i];
+        } else {
+            /* where this thread's codes go */
+            u32 bits = 0;
+            for (u32 i = a0; i < a1; i++) bits += len[in[i]];
+            const u32 incl = wave_scan_incl_u32(bits);
+            if (lane_id() == 63) wsum[wave_in_block()] = incl;
+            __syncthreads();
+            u32 pos = n_hdr_bits + incl - bits;
+            for (int k = 0; k < wave_in_block(); k++) pos += wsum[k];
+            if (bits) {
+                u32 w = pos >> 5;
+                u32 have = pos & 31u; /* low bits of the first word are somebody else's */
+                u64 acc = 0;
+                bool first = true;
+                for (u32 i = a0; i < a1; i++) {
+                    const u32 s = in[i];
+                    acc |= (u64)code[s] << have;
+                    have += len[s];
+                    if (have >= 32) {
+                        if (first) atomicOr(&out_w[w], (u32)acc);
+                        else out_w[w] = (u32)acc; /* (all 32 bits are this thread's) */
+                        first = false;
+                        w++;
+                        acc >>= 32;
+                        have -= 32;
+                    }
+                }
+                if (have) atomicOr(&out_w[w], (u32)acc);
+            }
+            __syncthreads();
+            const u8* ob = (const u8*)out_w;
+            for (u32 i = 16 * tid; i + 16 <= size; i += 16 * GZ_THREADS) {
+                u32x4 v;
+                v.x = out_w[i / 4], v.y = out_w[i / 4 + 1], v.z = out_w[i / 4 + 2], v.w = out_w[i / 4 + 3];
+                __builtin_memcpy(dst + i, &v, 16);
+            }
+            if (tid < (size & 15u)) dst[(size & ~15u) + tid] = ob[(size & ~15u) + tid];
+        }
+        if (tid == 0) blk_size[b] = size;
+    }
+}
+
+/* one block: blk_off[b] = bytes of the member in front of block b's; header, final block, trailer; hdr->gz_len, hdr->crc */
+__global__ void __launch_bounds__(1024)
+k_gz_finish(const u32* __restrict__ blk_size, const u32* __restrict__ blk_crc, u64* __restrict__ blk_off, GzHeader* __restrict__ hdr,
+            u8* __restrict__ out, u64 out_cap) {
+    __shared__ u64 wsum[16];
+    __shared__ u32 wcrc[16];
+    __shared__ u64 carry;
+    const u32 n_blocks = hdr->n_blocks;
+    if (threadIdx.x == 0) carry = 10;
+    u32 crc = 0;
+    __syncthreads();
+    for (u32 base = 0; base < n_blocks; base += 1024) { /* block-uniform */
+        const u32 i = base + threadIdx.x;
+        const u64 v = i < n_blocks ? blk_size[i] : 0u;
+        if (i < n_blocks) crc ^= blk_crc[i];
+        const u64 incl = gz_scan_incl_u64(v);
+        if (lane_id() == 63) wsum[wave_in_block()] = incl;
+        __syncthreads();
+        u64 run = carry + incl - v;
+        for (int k = 0; k < wave_in_block(); k++) run += wsum[k];
+        if (i < n_blocks) blk_off[i] = run;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = run + v;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) crc ^= shfl_xor_u32(crc, d);
+    if (lane_id() == 0) wcrc[wave_in_block()] = crc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const u64 total = hdr->total;
+        if (total == 0 || hdr->status) {
+            hdr->gz_len = 0;
+            return;
+        }
+        u32 raw = 0;
+        for (int k = 0; k < 16; k++) raw ^= wcrc[k];
+        /* the register starts as all ones: that is 0xFFFFFFFF * x^(8 total) on top of the remainder of the bytes */
+        const u32 c = raw ^ gz_mulmod(0xFFFFFFFFu, gz_xpow8(total)) ^ 0xFFFFFFFFu;
+        const u64 end = carry;
+        hdr->crc = c;
+        hdr->gz_len = end + 13;
+        if (end + 13 > out_cap) {
+            hdr->status = 1;
+            hdr->gz_len = 0;
+            return;
+        }
+        const u8 head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff}; /* deflate, no flags, no time, unknown system */
+        for (int k = 0; k < 10; k++) out[k] = head[k];
+        u8* t = out + end;
+        t[0] = 1, t[1] = 0, t[2] = 0, t[3] = 0xff, t[4] = 0xff; /* BFINAL, stored, 0 bytes */
+        for (int k = 0; k < 4; k++) t[5 + k] = (u8)(c >> (8 * k));
+        for (int k = 0; k < 4; k++) t[9 + k] = (u8)((u32)total >> (8 * k));
+    }
+}
+
+__global__ void __launch_bounds__(GZ_THREADS)
+k_gz_compact(const u8* __restrict__ tmp, const u64* __restrict__ blk_start, const u32* __restrict__ blk_size,
+             const u64* __restrict__ blk_off, const GzHeader* __restrict__ hdr, u8* __restrict__ out, u64 out_cap) {
+    const u32 n_blocks = hdr->n_blocks;
+    if (hdr->gz_len == 0) return;
+    for (u32 b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        const u8* src = tmp + blk_start[b] + (u64)GZ_SLACK * b;
+        const u32 size = blk_size[b];
+        if (blk_off[b] + size > out_cap) continue;
+        u8* dst = out + blk_off[b];
+        const u32 whole = size & ~15u;
+        for (u32 i = 16 * threadIdx.x; i < whole; i += 16 * GZ_THREADS) {
+            u32x4 v;
+            __builtin_memcpy(&v, src + i, 16);
+            __builtin_memcpy(dst + i, &v, 16);
+        }
+        if (threadIdx.x < (size & 15u)) dst[whole + threadIdx.x] = src[whole + threadIdx.x];
+    }
+}
+
+}  // namespace fpl
+#endif

@@ -24,6 +24,7 @@ EXPORTS = [
     "fpl_process_batch_async", "fpl_wait", "fpl_in_flight", "fpl_host_alloc", "fpl_host_free", "fpl_allreduce_counters",
     "fpl_count_end_kmers", "fpl_pick_adapter", "fpl_rccl_library", "fpl_comm_init", "fpl_get_batch_forms", "fpl_assume_inputs_ready",
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
+    "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam",
 ]
 
@@ -131,6 +132,14 @@ def load_library(path=None):
     L.fpl_cancel_text.argtypes = [C.c_void_p]
     L.fpl_wait_text.restype = C.c_int
     L.fpl_wait_text.argtypes = [C.c_void_p, C.POINTER(abi.FplTextResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "fpl_wait_text_gz"):  # (ABI v9; a stand-in library without the gzip calls still loads: gzip=True then raises)
+        L.fpl_set_text_gzip.restype = C.c_int
+        L.fpl_set_text_gzip.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_wait_text_gz.restype = C.c_int
+        L.fpl_wait_text_gz.argtypes = [C.c_void_p, C.POINTER(abi.FplTextResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.fpl_get_gzip_batches.restype = C.c_int
+        L.fpl_get_gzip_batches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.fpl_process_bam_async.restype = C.c_int
     L.fpl_process_bam_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
@@ -247,12 +256,18 @@ class Engine:
         """fpl_decode_bam on this engine's device -> (bases, qualities) as uint8 arrays of off[-1] bytes"""
         return decode_bam(self.device, bam, rec_start, off)
 
-    def submit_text(self, text):
+    def submit_text(self, text, gzip=False):
         """fpl_process_text_async: a chunk of FASTQ text (a pinned uint8 array: pinned_array) that starts at a record and ends
         behind one; the parse runs on the device"""
         self._keep_text = getattr(self, "_keep_text", []) + [text]
         self._keep_text = self._keep_text[-(abi.FPL_MAX_IN_FLIGHT + 1):]
+        if gzip or getattr(self, "_gz_on", False):  # (the switch is the context's: touched only when it has to change)
+            if not hasattr(self.L, "fpl_wait_text_gz"):
+                raise FplError("gzip=True needs fpl_set_text_gzip / fpl_wait_text_gz (C-ABI version 9)")
+            self._check(self.L.fpl_set_text_gzip(self.h, int(bool(gzip))), "fpl_set_text_gzip")
+            self._gz_on = bool(gzip)
         self._check(self.L.fpl_process_text_async(self.h, text.ctypes.data, len(text)), "fpl_process_text_async")
+        self._gz_flags = getattr(self, "_gz_flags", []) + [bool(gzip)]
 
     def peek_text(self):
         """fpl_peek_text: the parse's verdict for the oldest text batch (nothing of it is counted yet)"""
@@ -268,17 +283,27 @@ class Engine:
         self._check(self.L.fpl_cancel_text(self.h), "fpl_cancel_text")
 
     def wait_text(self):
-        """fpl_wait_text -> (fpl_text_result as a dict, records [n] as a numpy copy, line starts [n, 4] as a numpy copy)"""
+        """fpl_wait_text -> (fpl_text_result as a dict, records [n] as a numpy copy, line starts [n, 4] as a numpy copy); for a
+        batch submitted with gzip=True fpl_wait_text_gz, and a fourth item: the batch's gzip member as bytes (b"" when no read
+        passed)"""
         out = abi.FplTextResult()
         rp, lp = C.c_void_p(), C.c_void_p()
-        self._check(self.L.fpl_wait_text(self.h, C.byref(out), C.byref(rp), C.byref(lp)), "fpl_wait_text")
+        flags = getattr(self, "_gz_flags", [])
+        want_gz = flags.pop(0) if flags else False
+        if want_gz:
+            gp, gl = C.c_void_p(), C.c_uint64(0)
+            self._check(self.L.fpl_wait_text_gz(self.h, C.byref(out), C.byref(rp), C.byref(lp), C.byref(gp), C.byref(gl)), "fpl_wait_text_gz")
+            member = (C.string_at(gp.value, gl.value) if gl.value else b"",)
+        else:
+            self._check(self.L.fpl_wait_text(self.h, C.byref(out), C.byref(rp), C.byref(lp)), "fpl_wait_text")
+            member = ()
         info = {k: getattr(out, k) for k, _ in abi.FplTextResult._fields_}
         n = out.n_reads
         if out.status != 0 or n == 0:
-            return info, np.zeros(0, dtype=abi.RESULT_DTYPE), np.zeros((0, 4), np.uint32)
+            return (info, np.zeros(0, dtype=abi.RESULT_DTYPE), np.zeros((0, 4), np.uint32)) + member
         res = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_uint8)), shape=(n * 36,)).view(abi.RESULT_DTYPE).copy()
         lines = np.ctypeslib.as_array(C.cast(lp, C.POINTER(C.c_uint32)), shape=(n, 4)).copy()
-        return info, res, lines
+        return (info, res, lines) + member
 
     def in_flight(self):
         return int(self.L.fpl_in_flight(self.h))
@@ -372,6 +397,12 @@ class Engine:
         out = (C.c_uint64 * 6)()
         self._check(self.L.fpl_get_batch_forms(self.h, out), "fpl_get_batch_forms")
         return dict(batches=int(out[0]), reads=int(out[1]), trim_batched=int(out[2]), stats_sorted=int(out[3]), largest=int(out[4]), trims_ahead=int(out[5]))
+
+    def gzip_batches(self):
+        """batches whose gzip member was made on the device (fpl_get_gzip_batches)"""
+        out = C.c_uint64(0)
+        self._check(self.L.fpl_get_gzip_batches(self.h, C.byref(out)), "fpl_get_gzip_batches")
+        return int(out.value)
 
     def kernel_times(self):
         """-> ({kernel name: ms summed over the window}, n_batches)"""

@@ -85,7 +85,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""},
 };
 
 struct Args {
@@ -166,6 +166,8 @@ struct Work {
     vector<fpl_read_result> res;
     fplh::FragmentList frags; /* --break / --mask */
     vector<string> outs, faileds;
+    string gz_member;  /* --out *.gz deflated on the device (fpl_wait_text_gz): this batch's gzip member, written as it is */
+    bool dev_gz = false;
     vector<struct iovec> gather; /* --out as a gather list over the batch's own arrays (plain output, see build_gather) */
     string gather_text;          /* the few bytes of it that exist nowhere yet: names with a split prefix */
     int rc = 0;
@@ -765,6 +767,27 @@ int main(int argc, char* argv[]) {
         if (fstat(fileno(fout.f), &ost) == 0 && S_ISREG(ost.st_mode)) gatherOut = false;
     }
     if (gatherOut) fflush(fout.f); /* (from here on the descriptor is written directly) */
+    /* --out *.gz: the device composes and deflates the passing reads of every chunk IT parsed (fpl_set_text_gzip /
+       fpl_wait_text_gz, C-ABI version 9) and the writer appends the member; a chunk that falls back to the host's reader, and a
+       batch the library makes no member for, is formatted and deflated here as before -- members are self-contained, so the
+       two kinds mix in one file.  -z 5..9 ask for a smaller file than a Huffman-only coder gives and keep the host's deflate;
+       so do --failed_out's own file, --split*, --break / --mask (never text batches), BAM input, --host_parse, --host_gzip.
+       The entry points are looked up at run time: the binary starts against a library without them. */
+    typedef int (*SetTextGzipFn)(fpl_ctx*, int);
+    typedef int (*WaitTextGzFn)(fpl_ctx*, fpl_text_result*, const fpl_read_result**, const uint32_t**, const uint8_t**, uint64_t*);
+    WaitTextGzFn waitTextGz = nullptr;
+    bool devGz = false;
+    if (fout && fout.gz && textMode && !split && !fragmentMode && !cmd.exist("host_gzip") && cmd.i("compression") <= 4) {
+        SetTextGzipFn setTextGzip = (SetTextGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_text_gzip");
+        waitTextGz = (WaitTextGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_text_gz");
+        devGz = setTextGzip && waitTextGz;
+        for (int d = 0; devGz && d < nGpus; d++)
+            if (setTextGzip(dev[(size_t)d].ctx, 1) != FPL_OK) devGz = false;
+        if (!devGz)
+            for (int d = 0; setTextGzip && d < nGpus; d++) (void)setTextGzip(dev[(size_t)d].ctx, 0);
+    }
+    std::atomic<uint64_t> nDevGz{0};
+    if (devGz && cmd.exist("verbose")) cerr << "output: gzip members deflated on the device" << endl;
     /* formatter stage threads: one per device -- or four when the output is deflated, each with a quarter of the helpers:
        a batch of one chunk (32 MB of text) cut into 64 members keeps 64 helpers busy for a few milliseconds between two
        thread hand-offs (measured: 25 ms per batch, 1.3 GB/s), four batches side by side in 16 members each do not wait
@@ -1018,7 +1041,9 @@ int main(int argc, char* argv[]) {
                     fpl_text_result tr;
                     const fpl_read_result* rr = nullptr;
                     const uint32_t* ls = nullptr;
-                    const int rc = fpl_wait_text(ctx, &tr, &rr, &ls);
+                    const uint8_t* gzp = nullptr;
+                    uint64_t gzn = 0;
+                    const int rc = devGz ? waitTextGz(ctx, &tr, &rr, &ls, &gzp, &gzn) : fpl_wait_text(ctx, &tr, &rr, &ls);
                     if (f.state == TEXT_STARTED && w->rc == FPL_OK) {
                         if (rc != FPL_OK) fail(w, rc);
                         else if (tr.status != FPL_TEXT_OK) fail(w, FPL_ERR_STATE); /* (the verdict was "good") */
@@ -1026,6 +1051,11 @@ int main(int argc, char* argv[]) {
                             w->res.assign(rr, rr + tr.n_reads);
                             w->batch.adopt_lines(ls, tr.n_reads);
                             nTextBatches++;
+                            if (gzn) { /* (no member: nothing passed, or the library makes none -- the formatter's turn) */
+                                w->gz_member.assign((const char*)gzp, (size_t)gzn);
+                                w->dev_gz = true;
+                                nDevGz++;
+                            }
                         }
                     } else if (w && rc != FPL_OK && w->rc == FPL_OK) {
                         fail(w, rc);
@@ -1069,6 +1099,7 @@ int main(int argc, char* argv[]) {
                     w->res.resize(w->batch.n());
                     w->err.clear();
                     w->rc = FPL_OK;
+                    w->dev_gz = false;
                     if (textMode && !w->batch.text_backed && !w->verdict_done) {
                         /* a CSR batch in a run whose chunks the device parses (a chunk the sequencer parsed itself): its kernels
                            are enqueued by the submission, so it waits for the verdicts in front of it first -- with nothing of
@@ -1136,10 +1167,16 @@ int main(int argc, char* argv[]) {
                 const double t1 = now();
                 if (w->rc == FPL_OK && !split && gatherOut) {
                     build_gather(w->batch, w->res.data(), w->gather, w->gather_text);
+                } else if (w->rc == FPL_OK && w->dev_gz && !ffail) { /* --out is this batch's member as the device made it */
+                    w->outs.resize(1);
+                    w->outs[0].swap(w->gz_member);
                 } else if (w->rc == FPL_OK && !split) { /* (--split* output is cut per pack of 16 reads by the writer) */
                     fplh::format_batch_parallel(w->batch, w->res.data(), fmtThreads, w->outs, ffail ? &w->faileds : nullptr,
                                                 fragmentMode ? &w->frags : nullptr);
-                    if (fout && fout.gz) gzip_pieces(w->outs);
+                    if (w->dev_gz) { /* (formatted for --failed_out alone) */
+                        w->outs.resize(1);
+                        w->outs[0].swap(w->gz_member);
+                    } else if (fout && fout.gz) gzip_pieces(w->outs);
                     if (ffail && ffail.gz) gzip_pieces(w->faileds);
                 }
                 tFormat[f] += now() - t1;
@@ -1299,9 +1336,11 @@ int main(int argc, char* argv[]) {
             cerr << "device thread " << d << ": " << nSubmit[d] << " submissions " << tSubmit[d] << " s (mean depth behind them "
                  << (nSubmit[d] ? (double)depthSum[d] / (double)nSubmit[d] : 0.0) << "), queue empty with room for a batch " << nMiss[d]
                  << " times, nothing in flight and nothing parsed " << tStarved[d] << " s" << endl;
-    if (cmd.exist("verbose") && textMode)
+    if (cmd.exist("verbose") && textMode) {
+        if (devGz) cerr << "device gzip: " << nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
         cerr << "device parse: " << nTextBatches.load() << " chunks parsed on the device, " << nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;
+    }
     if (cmd.exist("verbose")) { /* which kernel forms the batches took: the library picks by batch size (csrc/pipeline.h) */
         uint64_t f[6] = {0, 0, 0, 0, 0, 0};
         for (auto& D : dev) {

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define FPL_ABI_VERSION 8
+#define FPL_ABI_VERSION 9
 
 /* limits */
 #define FPL_MAX_ADAPTER_LEN 255 /* longest adapter the device path accepts            */
@@ -319,7 +319,8 @@ int fpl_in_flight(const fpl_ctx* ctx);
  *                           the chunk held; results[i] is the record of read i and line_starts[4 i + j] the offset, in
  *                           `text`, of line j of record i (0 name, 1 bases, 2 '+', 3 qualities) -- so the caller formats its
  *                           output from the text it still holds.  Both arrays are the library's (page-locked) and stay valid
- *                           until the second submission after this one.
+ *                           until the next submission that takes this batch's slot (the FPL_MAX_IN_FLIGHT-th submission after
+ *                           the one that made this batch).
  *
  * status FPL_TEXT_IRREGULAR: the chunk is not "four lines per record, every line ended by \n or \r\n, '@' and '+' in place,
  * equal lengths" (blank lines, a lone \r, a missing final line break, a malformed record: bad_record is the first) -- NOTHING
@@ -347,6 +348,34 @@ int fpl_peek_text(fpl_ctx* ctx, fpl_text_result* out);
 int fpl_start_text(fpl_ctx* ctx);
 int fpl_cancel_text(fpl_ctx* ctx);
 int fpl_wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts);
+
+/*
+ * (ABI v9) The passing reads of a text batch as gzip, deflated on the device (csrc/gz_emit.h): what a host writes to an --out
+ * whose name ends in .gz, without formatting or deflating a byte itself.
+ *
+ *   fpl_set_text_gzip   a switch of the context, read by fpl_process_text_async: a text batch submitted while it is on is a
+ *                       GZIP batch.  Changes nothing about the batch's records, line starts or counters.
+ *   fpl_wait_text_gz    fpl_wait_text for the oldest batch in flight, plus its bytes: *gz points to *gz_len bytes that are one
+ *                       complete gzip member (RFC 1952; deflate blocks of literals with dynamic Huffman tables, stored blocks
+ *                       where a table would not pay) whose inflation is, byte for byte, what the host's formatter appends to
+ *                       --out for this batch from `results` and the text: every fragment with code FPL_PASS_FILTER of every read
+ *                       that was not dropped, in input order, lines ended by "\n".  Appending the members of successive batches
+ *                       to a file gives a valid .gz of the whole output.  *gz_len is 0 (and *gz NULL) when no read passed, when
+ *                       the batch's status is not FPL_TEXT_OK, or when the batch was submitted with the switch off.  The layout
+ *                       kernel is enqueued behind the batch's per-read kernels on their stream (by fpl_start_text or this call);
+ *                       THIS call reads its sizes back, sizes the buffers by them, enqueues the other kernels on the same stream
+ *                       and copies the member, on the copy stream, into a page-locked buffer of the batch's slot: two waits for
+ *                       the device beside the one for the records.  *gz is the library's and, like results and line_starts, stays
+ *                       valid until the next submission that takes this batch's slot.  A gzip batch may also be collected with
+ *                       fpl_wait_text: its bytes are then never made.
+ *                       Size: never more than 23 + n + 5 * (n / FPL_GZ_BLOCK_BYTES + 1 + 2 * fragments) bytes for n bytes of text.
+ *   fpl_get_gzip_batches  how many batches fpl_wait_text_gz has made members for (the sibling of fpl_get_batch_forms).
+ */
+#define FPL_GZ_BLOCK_BYTES 16384
+int fpl_set_text_gzip(fpl_ctx* ctx, int on);
+int fpl_wait_text_gz(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
+                     const uint8_t** gz, uint64_t* gz_len);
+int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out);
 
 /*
  * (ABI v8) BAM records in: the host inflates a BAM's BGZF blocks and walks its records (24 bytes of each: where it starts, its

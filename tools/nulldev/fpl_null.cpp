@@ -267,6 +267,20 @@ int fpl_reset_counters(fpl_ctx* ctx) {
 }
 int fpl_synchronize(fpl_ctx*) { return FPL_OK; }
 int fpl_assume_inputs_ready(fpl_ctx* ctx, int) { return ctx ? FPL_OK : FPL_ERR_ARG; }
+/* (ABI v9: no coder here -- the switch is accepted and no batch ever gets a member, so a host falls back to its own deflate) */
+int fpl_set_text_gzip(fpl_ctx* ctx, int) { return ctx ? FPL_OK : FPL_ERR_ARG; }
+int fpl_wait_text_gz(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
+                     const uint8_t** gz, uint64_t* gz_len) {
+    if (!gz || !gz_len) return FPL_ERR_ARG;
+    *gz = nullptr;
+    *gz_len = 0;
+    return fpl_wait_text(ctx, out, results, line_starts);
+}
+int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    *out = 0;
+    return FPL_OK;
+}
 int fpl_get_batch_forms(const fpl_ctx* ctx, uint64_t out[6]) { /* (no kernels here: nothing to report but zeros) */
     if (!ctx || !out) return FPL_ERR_ARG;
     for (int i = 0; i < 6; i++) out[i] = 0;
