@@ -132,7 +132,12 @@ struct fpl_ctx {
         u8* h_gz = nullptr; /* pinned */
         uint64_t h_gz_cap = 0;
         hipEvent_t ev_gz = nullptr;
-        /* a BAM batch (fpl_process_bam_async): the inflated record bytes and where every record starts; a CSR batch otherwise */
+        /* a BAM batch (fpl_process_bam_async): the inflated record bytes and where every record starts; a CSR batch otherwise.
+           bam_gz: a gzip BAM batch (fpl_set_bam_gzip) -- `gz` above with the BAM forms of the layout and compose kernels, which
+           read d_bam / d_rec / d_seq / d_qual / d_off / d_results of THIS slot: nothing touches them before the slot's next
+           submission, which comes after its wait */
+        bool bam_gz = false;
+        uint64_t bam_bases = 0;
         u8* d_bam = nullptr;
         uint64_t bam_cap = 0;
         uint64_t* d_rec = nullptr;
@@ -152,6 +157,7 @@ struct fpl_ctx {
     bool ev_ready = false; /* the whole event ring exists */
     uint64_t forms[6] = {0, 0, 0, 0, 0, 0}; /* fpl_get_batch_forms */
     bool text_gzip = false;    /* fpl_set_text_gzip */
+    bool bam_gzip = false;     /* fpl_set_bam_gzip */
     uint64_t gz_batches = 0;   /* fpl_get_gzip_batches */
     std::string err;
 };
@@ -964,7 +970,7 @@ static int ensure_text_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint64_t n_bytes) {
     return FPL_OK;
 }
 
-/* ---- gzip members of a text batch (ABI v9): csrc/gz_emit.h ---- */
+/* ---- gzip members of a text batch (ABI v9) and of a BAM batch (ABI v10): csrc/gz_emit.h ---- */
 static int gz_grow(fpl_ctx* ctx, void** p, uint64_t& cap, uint64_t want) { /* bytes; 25 % headroom; a grow waits for the device */
     if (want <= cap && *p) return FPL_OK;
     FPL_HIP(hipDeviceSynchronize());
@@ -982,7 +988,7 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
         FPL_HIP(hipMalloc((void**)&sl.d_gz_hdr, sizeof(GzHeader)));
         FPL_HIP(hipHostMalloc((void**)&sl.h_gz_hdr, sizeof(GzHeader), hipHostMallocDefault));
     }
-    const uint64_t blk_want = gz_blocks_bound(sl.text_bytes, n) + 1;
+    const uint64_t blk_want = (sl.bam_gz ? gz_bam_blocks_bound(sl.bam_bases, n) : gz_blocks_bound(sl.text_bytes, n)) + 1;
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
     if ((uint64_t)n + 1 > sl.gz_rec_cap || !sl.d_rec_off) {
         uint64_t cap = 0;
@@ -1007,8 +1013,13 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
         sl.gz_blk_cap = (u32)cap;
     }
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
-                       (const fpl_read_result*)sl.d_results, n, sl.d_rec_off, sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
+    if (sl.bam_gz)
+        hipLaunchKernelGGL(k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_bam, (const uint64_t*)sl.d_rec, (const u8*)sl.d_seq,
+                           (const u8*)sl.d_qual, (const uint64_t*)sl.d_off, (const fpl_read_result*)sl.d_results, n, sl.d_rec_off,
+                           sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
+    else
+        hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
+                           (const fpl_read_result*)sl.d_results, n, sl.d_rec_off, sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
     FPL_HIP(hipGetLastError());
     FPL_HIP(hipMemcpyAsync(sl.h_gz_hdr, sl.d_gz_hdr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
     FPL_HIP(hipEventRecord(sl.ev_gz, st));
@@ -1041,8 +1052,13 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
         sl.gz_out_cap = std::min(c1, c2);
     }
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
-                       (const fpl_read_result*)sl.d_results, n, (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
+    if (sl.bam_gz)
+        hipLaunchKernelGGL(k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_bam, (const uint64_t*)sl.d_rec,
+                           (const u8*)sl.d_seq, (const u8*)sl.d_qual, (const uint64_t*)sl.d_off, (const fpl_read_result*)sl.d_results, n,
+                           (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
+    else
+        hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line,
+                           (const u32*)sl.d_nl, (const fpl_read_result*)sl.d_results, n, (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
     const u32 grid = std::max<u32>(1u, std::min<u32>(h.n_blocks, 8u * ctx->n_cu));
     hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)sl.d_gz_comp, (const u64*)sl.d_gz_blk_start,
                        (const GzHeader*)sl.d_gz_hdr, sl.d_gz_tmp, sl.d_gz_blk_size, sl.d_gz_blk_crc);
@@ -1124,6 +1140,7 @@ int fpl_process_text_async(fpl_ctx* ctx, const uint8_t* text, uint64_t n_bytes) 
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = 1;
     sl.gz = ctx->text_gzip;
+    sl.bam_gz = false;
     sl.stage = 2;
     sl.cancelled = false;
     sl.n_reads = 0;
@@ -1286,7 +1303,8 @@ static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result**
 
 int fpl_in_flight(const fpl_ctx* ctx) { return ctx ? (int)(ctx->submitted - ctx->waited) : 0; }
 
-int fpl_wait(fpl_ctx* ctx) {
+/* gz != nullptr: fpl_wait_bam_gz -- the member of a gzip BAM batch is made before the records are handed over */
+static int wait_batch(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx) return FPL_ERR_ARG;
     if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
     fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
@@ -1295,8 +1313,25 @@ int fpl_wait(fpl_ctx* ctx) {
     if (sl.rc != FPL_OK) return sl.rc; /* nothing was enqueued behind the failure */
     if (sl.n_reads == 0) return FPL_OK;
     FPL_HIP(hipSetDevice(ctx->device));
+    if (gz && sl.gz && sl.bam_gz) {
+        const int r = gz_emit(ctx, sl, gz, gz_len);
+        if (r != FPL_OK) return r;
+    }
     FPL_HIP(hipEventSynchronize(sl.ev_done));
     memcpy(sl.user_results, sl.h_results, sizeof(fpl_read_result) * (size_t)sl.n_reads);
+    return FPL_OK;
+}
+int fpl_wait(fpl_ctx* ctx) { return wait_batch(ctx, nullptr, nullptr); }
+int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
+    if (!gz || !gz_len) return FPL_ERR_ARG;
+    *gz = nullptr;
+    *gz_len = 0;
+    return wait_batch(ctx, gz, gz_len);
+}
+int fpl_set_bam_gzip(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    if (on && ctx->hcfg.defer) return FPL_ERR_STATE; /* (--break / --mask write from fragment lists) */
+    ctx->bam_gzip = on != 0;
     return FPL_OK;
 }
 
@@ -1312,6 +1347,7 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
        the slots are collected in the order of submission) */
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = 0;
+    sl.gz = sl.bam_gz = false;
     sl.n_reads = n_reads;
     sl.user_results = results;
     sl.rc = FPL_OK;
@@ -1401,7 +1437,9 @@ static void bam_launch(const u8* d_bam, const uint64_t* d_rec, const uint64_t* d
 int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off,
                           uint32_t n_reads, uint8_t* seq_out, uint8_t* qual_out, fpl_read_result* results) {
     if (!ctx) return FPL_ERR_ARG;
-    if (n_reads && (!bam || !rec_start || !off || !seq_out || !qual_out || !results)) return FPL_ERR_ARG;
+    if (n_reads && (!bam || !rec_start || !off || !results)) return FPL_ERR_ARG;
+    /* (a gzip batch may leave the decoded arrays on the device: both NULL or neither) */
+    if (n_reads && (!seq_out || !qual_out) && !(ctx->bam_gzip && !seq_out && !qual_out)) return FPL_ERR_ARG;
     if (ctx->submitted - ctx->waited >= FPL_MAX_IN_FLIGHT) return FPL_ERR_STATE;
     FPL_HIP(hipSetDevice(ctx->device));
     if (ctx->hcfg.defer && ctx->submitted != ctx->waited) return FPL_ERR_STATE; /* (--break / --mask: as fpl_process_batch_async) */
@@ -1412,6 +1450,7 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
     }
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = 0; /* (collected by fpl_wait like a CSR batch) */
+    sl.gz = sl.bam_gz = ctx->bam_gzip;
     sl.n_reads = n_reads;
     sl.user_results = results;
     sl.rc = FPL_OK;
@@ -1420,6 +1459,7 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         return FPL_OK;
     }
     const uint64_t o_begin = off[0], o_end = off[n_reads];
+    sl.bam_bases = o_end - o_begin;
     int r = ensure_host_streams(ctx);
     if (r != FPL_OK) return r;
     r = ensure_slot(ctx, sl, n_reads, o_end + 16); /* (the decode writes whole 16-byte words) */
@@ -1460,7 +1500,7 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         if (rd != FPL_OK) return rd;
         FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
         FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_parsed, 0));
-        if (o_end > o_begin) {
+        if (o_end > o_begin && seq_out) {
             FPL_HIP(hipMemcpyAsync(seq_out + o_begin, sl.d_seq + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
             FPL_HIP(hipMemcpyAsync(qual_out + o_begin, sl.d_qual + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
         }
@@ -1468,6 +1508,7 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         FPL_HIP(hipMemcpyAsync(sl.h_results, sl.d_results, sizeof(fpl_read_result) * (size_t)n_reads, hipMemcpyDeviceToHost,
                                ctx->s_d2h));
         FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
+        if (sl.gz) return gz_layout(ctx, sl, n_reads); /* (behind the per-read kernels, on their stream) */
         return FPL_OK;
     };
     r = enqueue();

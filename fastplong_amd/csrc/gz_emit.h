@@ -1,8 +1,11 @@
 /*
- * gz_emit.h -- the passing reads of a TEXT batch as gzip members, composed and Huffman-coded ON THE DEVICE
- * (fpl_set_text_gzip / fpl_wait_text_gz, include/fastplong_amd.h).
+ * gz_emit.h -- the passing reads of a TEXT batch or a BAM batch as gzip members, composed and Huffman-coded ON THE DEVICE
+ * (fpl_set_text_gzip / fpl_wait_text_gz, fpl_set_bam_gzip / fpl_wait_bam_gz, include/fastplong_amd.h).
  *
- * Input: the chunk's text, where its lines start and end (text_parse.h: line[], nl_pos[]) and the per-read records.  Output: one
+ * Input: the per-read records and a record source -- the chunk's text with where its lines start and end (text_parse.h: line[],
+ * nl_pos[]: GzTextSrc), or a BAM batch's record bytes, record starts, decoded bases / qualities and CSR offsets (bam_decode.h:
+ * GzBamSrc).  k_gz_layout / k_gz_compose are the text forms and k_gz_layout_bam / k_gz_compose_bam the BAM forms of ONE body each,
+ * templated on the source, so the cuts and the length arithmetic exist once.  Output: one
  * gzip member (RFC 1952) whose inflation is exactly what fplh::format_batch (host/fastq.cpp, format_range without a fragment
  * list) appends for that batch; nothing at all when no read passed.  Long-read FASTQ has next to nothing for LZ77 to find, so the
  * deflate stream holds literals only: the gain is the entropy code, and blocks are cut so that bases and qualities -- which share
@@ -58,6 +61,10 @@ struct GzHeader {
    name and the '+' line, and each may start two blocks) */
 inline u64 gz_total_bound(u64 text_bytes, u64 n_rec) { return 2 * text_bytes + 46 * n_rec; }
 inline u64 gz_blocks_bound(u64 text_bytes, u64 n_rec) { return gz_total_bound(text_bytes, n_rec) / GZ_B + 2 + 4 * n_rec; }
+/* the same for a BAM batch of n_bases bases: a fragment is at most its read, and writes a name line of at most 1 + 254 + 23 bytes,
+   the '+' line and four line ends besides its bases and qualities */
+inline u64 gz_bam_total_bound(u64 n_bases, u64 n_rec) { return 4 * n_bases + 2 * (255 + 23 + 6) * n_rec; }
+inline u64 gz_bam_blocks_bound(u64 n_bases, u64 n_rec) { return gz_bam_total_bound(n_bases, n_rec) / GZ_B + 2 + 4 * n_rec; }
 
 /* ---- CRC-32 arithmetic (reflected: bit 31 is x^0) ---- */
 __device__ __forceinline__ u32 gz_mulmod(u32 a, u32 b) { /* a * b mod P */
@@ -84,24 +91,88 @@ __device__ __forceinline__ u32 gz_crc_table_entry(u32 i) {
 }
 
 /* ---- what a read writes ---- */
+/* The pieces of one record, whatever the batch came in as.  The name line is `lead`, the prefix of a split read, and the
+   name_len - 1 bytes at name_rest; name_len counts the lead (0: an empty line, nothing is written).  strand == nullptr says the
+   '+' line is the one byte '+'.  seq / qual are the read's first base and quality: pointers, so a batch may pass 4 GiB. */
 struct GzRec {
-    u32 name_at, name_len, strand_at, strand_len, seq_at, qual_at;
+    const u8* name_rest;
+    const u8* strand;
+    const u8* seq;
+    const u8* qual;
+    u32 name_len, strand_len;
+    u8 lead;
 };
 __device__ __forceinline__ u32 gz_line_len(const u8* __restrict__ text, u32 at, u32 nl) {
     u32 e = nl; /* the '\n' */
     if (e > at && text[e - 1] == '\r') e--;
     return e - at;
 }
-__device__ __forceinline__ GzRec gz_rec(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos, u32 r) {
-    GzRec g;
-    g.name_at = line[4 * (size_t)r];
-    g.seq_at = line[4 * (size_t)r + 1];
-    g.strand_at = line[4 * (size_t)r + 2];
-    g.qual_at = line[4 * (size_t)r + 3];
-    g.name_len = gz_line_len(text, g.name_at, nl_pos[4 * (size_t)r]);
-    g.strand_len = gz_line_len(text, g.strand_at, nl_pos[4 * (size_t)r + 2]);
-    return g;
-}
+/* where the records come from: a type with rec(r).  The layout and compose kernels are templated on it, so that the cuts and the
+   length arithmetic exist once. */
+/* a TEXT batch: the chunk's text through the line starts and line ends text_parse.h found */
+struct GzTextSrc {
+    const u8* text;
+    const u32* line;
+    const u32* nl_pos;
+    __device__ __forceinline__ GzRec rec(u32 r) const {
+        GzRec g;
+        const u32 name_at = line[4 * (size_t)r], strand_at = line[4 * (size_t)r + 2];
+        g.seq = text + line[4 * (size_t)r + 1];
+        g.qual = text + line[4 * (size_t)r + 3];
+        g.name_len = gz_line_len(text, name_at, nl_pos[4 * (size_t)r]);
+        g.strand_len = gz_line_len(text, strand_at, nl_pos[4 * (size_t)r + 2]);
+        g.lead = g.name_len ? text[name_at] : (u8)0;
+        g.name_rest = text + name_at + 1;
+        g.strand = text + strand_at;
+        return g;
+    }
+    /* the same for a whole wave that asks for one record (k_gz_compose) */
+    __device__ __forceinline__ GzRec rec_wave(u32 r) const { return rec(r); }
+};
+/* a BAM batch (bam_decode.h): the name out of the record -- '@' and the l_read_name - 1 bytes at record + 36, so the line is never
+   empty --, the bases and qualities out of the decoded arrays (already the twin's: reversed for flag 0x10, min(q, 93) + 33) */
+struct GzBamSrc {
+    const u8* bam;
+    const uint64_t* rec_start;
+    const u8* seq;
+    const u8* qual;
+    const uint64_t* off;
+    /* the name ends at its first NUL, as the host's reader takes it (host/bam.cpp): l_read_name - 1 bytes in every BAM that keeps
+       to the format; 8 bytes a step (the record buffer holds BAM_PAD bytes behind its end) */
+    static __device__ __forceinline__ u32 name_bytes(const u8* rc) {
+        const u32 cap = rc[12] ? rc[12] - 1u : 0u;
+        u32 nl = 0;
+        for (; nl < cap; nl += 8) {
+            u64 w;
+            __builtin_memcpy(&w, rc + 36 + nl, 8);
+            const u64 z = (w - 0x0101010101010101ull) & ~w & 0x8080808080808080ull;
+            if (z) {
+                nl += (u32)__builtin_ctzll(z) >> 3;
+                break;
+            }
+        }
+        return nl < cap ? nl : cap;
+    }
+    __device__ __forceinline__ GzRec rec(u32 r) const { return make(r, name_bytes(bam + rec_start[r])); }
+    /* a whole wave asks for one record: lane 0 walks the name, the others take its answer */
+    __device__ __forceinline__ GzRec rec_wave(u32 r) const {
+        u32 nl = 0;
+        if (lane_id() == 0) nl = name_bytes(bam + rec_start[r]);
+        return make(r, shfl_u32(nl, 0));
+    }
+    __device__ __forceinline__ GzRec make(u32 r, u32 nl) const {
+        GzRec g;
+        const u8* rc = bam + rec_start[r];
+        g.name_len = 1u + nl; /* (the '@' is always there: a BAM name line is never empty) */
+        g.lead = (u8)'@';
+        g.name_rest = rc + 36;
+        g.strand = nullptr;
+        g.strand_len = 1;
+        g.seq = seq + off[r];
+        g.qual = qual + off[r];
+        return g;
+    }
+};
 __device__ __forceinline__ u32 gz_prefix_len(u32 kind, u32 name_len) { /* "split-by-adapter-left-" / "split-by-adapter-right-" */
     return name_len == 0 ? 0u : (kind == 1 ? 22u : (kind == 2 ? 23u : 0u));
 }
@@ -146,10 +217,9 @@ __device__ __forceinline__ u64 gz_scan_incl_u64(u64 v) {
 
 /* one block.  rec_off[r] = where record r's output starts (n_rec + 1 entries), blk_start[b] = where deflate block b starts
    (n_blocks + 1 entries, the last one the total) */
-__global__ void __launch_bounds__(1024)
-k_gz_layout(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
-            const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap,
-            GzHeader* __restrict__ hdr) {
+template <class Src>
+__device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off,
+                                               u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
     __shared__ u64 wsum[16];
     __shared__ u64 carry_len, carry_blk;
     if (threadIdx.x == 0) carry_len = 0, carry_blk = 0;
@@ -160,7 +230,7 @@ k_gz_layout(const u8* __restrict__ text, const u32* __restrict__ line, const u32
         fpl_read_result r = {};
         u64 len = 0;
         if (i < n_rec) {
-            g = gz_rec(text, line, nl_pos, i);
+            g = src.rec(i);
             r = res[i];
             if (!r.dropped)
                 for (int f = 0; f < r.n_frag && f < 2; f++)
@@ -214,6 +284,20 @@ k_gz_layout(const u8* __restrict__ text, const u32* __restrict__ line, const u32
     }
 }
 
+__global__ void __launch_bounds__(1024)
+k_gz_layout(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+            const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap,
+            GzHeader* __restrict__ hdr) {
+    gz_layout_body(GzTextSrc{text, line, nl_pos}, res, n_rec, rec_off, blk_start, blk_cap, hdr);
+}
+/* the BAM form: the slot of a batch fpl_process_bam_async decoded */
+__global__ void __launch_bounds__(1024)
+k_gz_layout_bam(const u8* __restrict__ bam, const uint64_t* __restrict__ rec_start, const u8* __restrict__ seq, const u8* __restrict__ qual,
+                const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off,
+                u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
+    gz_layout_body(GzBamSrc{bam, rec_start, seq, qual, off}, res, n_rec, rec_off, blk_start, blk_cap, hdr);
+}
+
 /* len bytes, the wave together; neither side is aligned */
 __device__ __forceinline__ void gz_wave_copy(u8* __restrict__ dst, const u8* __restrict__ src, u32 len) {
     const u32 lane = (u32)lane_id();
@@ -227,37 +311,36 @@ __device__ __forceinline__ void gz_wave_copy(u8* __restrict__ dst, const u8* __r
 }
 
 /* a wave per record; comp holds hdr->total bytes (the caller sized it after k_gz_layout: comp_cap is checked all the same) */
-__global__ void __launch_bounds__(256)
-k_gz_compose(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
-             const fpl_read_result* __restrict__ res, u32 n_rec, const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+template <class Src>
+__device__ __forceinline__ void gz_compose_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec,
+                                                const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
     const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     const u32 lane = (u32)lane_id();
     for (u32 i = wave; i < n_rec; i += n_waves) { /* wave-uniform */
         const u64 o0 = rec_off[i], o1 = rec_off[i + 1];
         if (o1 == o0 || o1 > comp_cap) continue;
-        const GzRec g = gz_rec(text, line, nl_pos, i);
+        const GzRec g = src.rec_wave(i);
         const fpl_read_result r = res[i];
         u8* d = comp + o0;
         for (int f = 0; f < r.n_frag && f < 2; f++) {
             if (r.code[f] != FPL_PASS_FILTER) continue;
             const u32 pl = gz_prefix_len(r.kind[f], g.name_len);
             const u32 fl = r.frag_len[f], fs = r.frag_start[f];
-            if (pl) {
-                if (lane == 0) d[0] = text[g.name_at];
+            if (g.name_len) {
+                if (lane == 0) d[0] = g.lead;
                 if (lane < pl) {
                     const char* pf = pl == 22 ? "split-by-adapter-left-" : "split-by-adapter-right-";
                     d[1 + lane] = (u8)pf[lane];
                 }
-                gz_wave_copy(d + 1 + pl, text + g.name_at + 1, g.name_len - 1);
-            } else {
-                gz_wave_copy(d, text + g.name_at, g.name_len);
+                gz_wave_copy(d + 1 + pl, g.name_rest, g.name_len - 1);
             }
             d += g.name_len + pl;
-            gz_wave_copy(d + 1, text + g.seq_at + fs, fl);
+            gz_wave_copy(d + 1, g.seq + fs, fl);
             u8* d2 = d + 1 + fl + 1;
-            gz_wave_copy(d2, text + g.strand_at, g.strand_len);
+            if (g.strand) gz_wave_copy(d2, g.strand, g.strand_len); /* (wave-uniform) */
+            else if (lane == 0) d2[0] = '+';
             u8* d3 = d2 + g.strand_len + 1;
-            gz_wave_copy(d3, text + g.qual_at + fs, fl);
+            gz_wave_copy(d3, g.qual + fs, fl);
             if (lane == 0) {
                 d[0] = '\n';
                 d2[-1] = '\n';
@@ -267,6 +350,17 @@ k_gz_compose(const u8* __restrict__ text, const u32* __restrict__ line, const u3
             d = d3 + fl + 1;
         }
     }
+}
+__global__ void __launch_bounds__(256)
+k_gz_compose(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+             const fpl_read_result* __restrict__ res, u32 n_rec, const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+    gz_compose_body(GzTextSrc{text, line, nl_pos}, res, n_rec, rec_off, comp, comp_cap);
+}
+__global__ void __launch_bounds__(256)
+k_gz_compose_bam(const u8* __restrict__ bam, const uint64_t* __restrict__ rec_start, const u8* __restrict__ seq, const u8* __restrict__ qual,
+                 const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_rec, const u64* __restrict__ rec_off,
+                 u8* __restrict__ comp, u64 comp_cap) {
+    gz_compose_body(GzBamSrc{bam, rec_start, seq, qual, off}, res, n_rec, rec_off, comp, comp_cap);
 }
 
 /* ---- code lengths: the whole workgroup; everything in LDS ---- */

@@ -25,7 +25,7 @@ EXPORTS = [
     "fpl_count_end_kmers", "fpl_pick_adapter", "fpl_rccl_library", "fpl_comm_init", "fpl_get_batch_forms", "fpl_assume_inputs_ready",
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
-    "fpl_process_bam_async", "fpl_decode_bam",
+    "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
 ]
 
 
@@ -145,6 +145,11 @@ def load_library(path=None):
                                         C.c_void_p, C.c_void_p]
     L.fpl_decode_bam.restype = C.c_int
     L.fpl_decode_bam.argtypes = [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "fpl_wait_bam_gz"):  # (ABI v10; as above: without them submit_bam(gzip=True) raises)
+        L.fpl_set_bam_gzip.restype = C.c_int
+        L.fpl_set_bam_gzip.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_wait_bam_gz.restype = C.c_int
+        L.fpl_wait_bam_gz.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -191,6 +196,8 @@ class Engine:
             raise FplError("fpl_create: %s" % self.L.fpl_strerror(rc).decode())
         self.h = h
         self.device = device
+        self._bam_gz_on = False   # the context's fpl_set_bam_gzip switch as this front end last set it
+        self._bam_gz_flags = []   # one entry per CSR / BAM batch in flight, oldest first: submitted with gzip=True?
 
     def _check(self, rc, what):
         if rc != 0:
@@ -239,18 +246,46 @@ class Engine:
         n = len(off) - 1
         self._check(self.L.fpl_process_batch_async(self.h, seq.ctypes.data, qual.ctypes.data, off.ctypes.data, n,
                                                    res.ctypes.data), "fpl_process_batch_async")
+        self._bam_gz_flags.append(False)
 
-    def wait(self):
-        self._check(self.L.fpl_wait(self.h), "fpl_wait")
+    def wait(self, member=True):
+        """fpl_wait for the oldest CSR / BAM batch -> None; for a batch submitted with submit_bam(gzip=True) fpl_wait_bam_gz -> the
+        batch's gzip member as bytes (b"" when no read passed).  member=False: plain fpl_wait for such a batch too -- its bytes are
+        then never made."""
+        want = bool(member and self._bam_gz_flags and self._bam_gz_flags[0])
+        gp, gl = C.c_void_p(), C.c_uint64(0)
+        rc = self.L.fpl_wait_bam_gz(self.h, C.byref(gp), C.byref(gl)) if want else self.L.fpl_wait(self.h)
+        # FPL_ERR_STATE / FPL_ERR_ARG: nothing was collected (nothing in flight, or a text batch is the oldest) and the library's
+        # queue is as it was; after any other outcome the batch has left it
+        if rc not in (abi.FPL_ERR_STATE, abi.FPL_ERR_ARG) and self._bam_gz_flags:
+            self._bam_gz_flags.pop(0)
+        self._check(rc, "fpl_wait_bam_gz" if want else "fpl_wait")
+        if not want:
+            return None
+        return C.string_at(gp.value, gl.value) if gl.value else b""
 
-    def submit_bam(self, bam, rec_start, off, seq_out, qual_out, res):
+    def submit_bam(self, bam, rec_start, off, seq_out=None, qual_out=None, res=None, gzip=False):
         """fpl_process_bam_async: inflated BAM record bytes (uint8, with at least one addressable byte), where each record
         starts (uint64), the output CSR offsets (uint64, n + 1); the decoded bases and qualities land in seq_out / qual_out
-        (pinned_array views of >= off[-1] bytes) and the records in res.  Everything must stay alive until wait()."""
+        (pinned_array views of >= off[-1] bytes) and the records in res.  Everything must stay alive until wait().
+        gzip=True: the passing reads also come back as a gzip member, composed and deflated on the device -- wait() returns it;
+        seq_out / qual_out may then both be None, and the decoded arrays stay on the device."""
         n = len(off) - 1
+        if res is None:
+            raise FplError("submit_bam: res is required")
+        if (seq_out is None) != (qual_out is None) or (seq_out is None and not gzip):
+            raise FplError("submit_bam: seq_out and qual_out may be left out only together, and only with gzip=True")
+        if gzip or self._bam_gz_on:  # (the switch is the context's: touched only when it has to change)
+            if not hasattr(self.L, "fpl_wait_bam_gz"):
+                raise FplError("gzip=True needs fpl_set_bam_gzip / fpl_wait_bam_gz (C-ABI version 10)")
+            self._check(self.L.fpl_set_bam_gzip(self.h, int(bool(gzip))), "fpl_set_bam_gzip")
+            self._bam_gz_on = bool(gzip)
         self._keep_bam = (getattr(self, "_keep_bam", []) + [(bam, rec_start, off)])[-(abi.FPL_MAX_IN_FLIGHT + 1):]
         self._check(self.L.fpl_process_bam_async(self.h, bam.ctypes.data, len(bam), rec_start.ctypes.data, off.ctypes.data, n,
-                                                 seq_out.ctypes.data, qual_out.ctypes.data, res.ctypes.data), "fpl_process_bam_async")
+                                                 seq_out.ctypes.data if seq_out is not None else None,
+                                                 qual_out.ctypes.data if qual_out is not None else None, res.ctypes.data),
+                    "fpl_process_bam_async")
+        self._bam_gz_flags.append(bool(gzip))
 
     def decode_bam(self, bam, rec_start, off):
         """fpl_decode_bam on this engine's device -> (bases, qualities) as uint8 arrays of off[-1] bytes"""

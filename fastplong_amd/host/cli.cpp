@@ -85,7 +85,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""},
 };
 
 struct Args {
@@ -168,6 +168,7 @@ struct Work {
     vector<string> outs, faileds;
     string gz_member;  /* --out *.gz deflated on the device (fpl_wait_text_gz): this batch's gzip member, written as it is */
     bool dev_gz = false;
+    bool dev_gz_empty = false; /* a gzip BAM batch in which nothing passed: --out gets nothing, and the decoded arrays may never have come back */
     vector<struct iovec> gather; /* --out as a gather list over the batch's own arrays (plain output, see build_gather) */
     string gather_text;          /* the few bytes of it that exist nowhere yet: names with a split prefix */
     int rc = 0;
@@ -771,7 +772,7 @@ int main(int argc, char* argv[]) {
        fpl_wait_text_gz, C-ABI version 9) and the writer appends the member; a chunk that falls back to the host's reader, and a
        batch the library makes no member for, is formatted and deflated here as before -- members are self-contained, so the
        two kinds mix in one file.  -z 5..9 ask for a smaller file than a Huffman-only coder gives and keep the host's deflate;
-       so do --failed_out's own file, --split*, --break / --mask (never text batches), BAM input, --host_parse, --host_gzip.
+       so do --failed_out's own file, --split*, --break / --mask (never text batches), --host_parse, --host_gzip.
        The entry points are looked up at run time: the binary starts against a library without them. */
     typedef int (*SetTextGzipFn)(fpl_ctx*, int);
     typedef int (*WaitTextGzFn)(fpl_ctx*, fpl_text_result*, const fpl_read_result**, const uint32_t**, const uint8_t**, uint64_t*);
@@ -786,8 +787,27 @@ int main(int argc, char* argv[]) {
         if (!devGz)
             for (int d = 0; setTextGzip && d < nGpus; d++) (void)setTextGzip(dev[(size_t)d].ctx, 0);
     }
+    /* the same for BAM input (fpl_set_bam_gzip / fpl_wait_bam_gz, C-ABI version 10): the device composes the member from the
+       records' names and the bases it decoded, under the same conditions with "parsed on the device" replaced by "BAM-backed
+       batch" -- and with --device_gzip asked for: whether this form beats the host's deflate beside the BGZF inflate on the
+       same CPUs has not been measured, so a BAM run keeps the host's path unless told otherwise.  Without --failed_out the decoded arrays are not even copied back (seq_out / qual_out NULL): the host formats
+       nothing of such a batch. */
+    typedef int (*SetBamGzipFn)(fpl_ctx*, int);
+    typedef int (*WaitBamGzFn)(fpl_ctx*, const uint8_t**, uint64_t*);
+    WaitBamGzFn waitBamGz = nullptr;
+    bool devBamGz = false;
+    if (fout && fout.gz && bamIn && cmd.exist("device_gzip") && !split && !fragmentMode && !cmd.exist("host_gzip") && cmd.i("compression") <= 4) {
+        SetBamGzipFn setBamGzip = (SetBamGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_gzip");
+        waitBamGz = (WaitBamGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_bam_gz");
+        devBamGz = setBamGzip && waitBamGz;
+        for (int d = 0; devBamGz && d < nGpus; d++)
+            if (setBamGzip(dev[(size_t)d].ctx, 1) != FPL_OK) devBamGz = false;
+        if (!devBamGz)
+            for (int d = 0; setBamGzip && d < nGpus; d++) (void)setBamGzip(dev[(size_t)d].ctx, 0);
+    }
+    const bool bamKeepArrays = !devBamGz || ffail; /* (--failed_out is formatted on the host: it needs the decoded bases) */
     std::atomic<uint64_t> nDevGz{0};
-    if (devGz && cmd.exist("verbose")) cerr << "output: gzip members deflated on the device" << endl;
+    if ((devGz || devBamGz) && cmd.exist("verbose")) cerr << "output: gzip members deflated on the device" << endl;
     /* formatter stage threads: one per device -- or four when the output is deflated, each with a quarter of the helpers:
        a batch of one chunk (32 MB of text) cut into 64 members keeps 64 helpers busy for a few milliseconds between two
        thread hand-offs (measured: 25 ms per batch, 1.3 GB/s), four batches side by side in 16 members each do not wait
@@ -1023,8 +1043,17 @@ int main(int argc, char* argv[]) {
                 const double t0 = now();
                 if (f.state == CSR) {
                     if (w->rc == FPL_OK) {
-                        const int rc = fpl_wait(ctx);
+                        const uint8_t* gzp = nullptr;
+                        uint64_t gzn = 0;
+                        const int rc = devBamGz && w->batch.bam_backed ? waitBamGz(ctx, &gzp, &gzn) : fpl_wait(ctx);
                         if (rc != FPL_OK) fail(w, rc);
+                        else if (gzn) {
+                            w->gz_member.assign((const char*)gzp, (size_t)gzn);
+                            w->dev_gz = true;
+                            nDevGz++;
+                        } else if (devBamGz && w->batch.bam_backed) { /* no member: nothing of this batch passed */
+                            w->dev_gz_empty = true;
+                        }
                     }
                     if (w->rc == FPL_OK && fragmentMode) { /* any number of output reads per read: fetch the list */
                         uint32_t nf = 0, nr = 0;
@@ -1100,6 +1129,7 @@ int main(int argc, char* argv[]) {
                     w->err.clear();
                     w->rc = FPL_OK;
                     w->dev_gz = false;
+                    w->dev_gz_empty = false;
                     if (textMode && !w->batch.text_backed && !w->verdict_done) {
                         /* a CSR batch in a run whose chunks the device parses (a chunk the sequencer parsed itself): its kernels
                            are enqueued by the submission, so it waits for the verdicts in front of it first -- with nothing of
@@ -1120,7 +1150,8 @@ int main(int argc, char* argv[]) {
                         w->rc = fpl_process_text_async(ctx, w->batch.raw.data() + w->batch.raw_begin, w->batch.raw_len);
                     else if (w->batch.bam_backed) /* (the device decodes the bases into the batch's own page-locked arrays) */
                         w->rc = bamAsync(ctx, w->batch.bam.data(), w->batch.bam.size(), w->batch.rec_start.data(), w->batch.off.data(),
-                                         w->batch.n(), w->batch.seq.data(), w->batch.qual.data(), w->res.data());
+                                         w->batch.n(), bamKeepArrays ? w->batch.seq.data() : nullptr,
+                                         bamKeepArrays ? w->batch.qual.data() : nullptr, w->res.data());
                     else
                         w->rc = fpl_process_batch_async(ctx, w->batch.seq.data(), w->batch.qual.data(), w->batch.off.data(), w->batch.n(),
                                                         w->res.data());
@@ -1170,6 +1201,9 @@ int main(int argc, char* argv[]) {
                 } else if (w->rc == FPL_OK && w->dev_gz && !ffail) { /* --out is this batch's member as the device made it */
                     w->outs.resize(1);
                     w->outs[0].swap(w->gz_member);
+                } else if (w->rc == FPL_OK && w->dev_gz_empty && !ffail) {
+                    /* nothing to write, and nothing to format from: without --failed_out the batch's bases stayed on the device */
+                    w->outs.clear();
                 } else if (w->rc == FPL_OK && !split) { /* (--split* output is cut per pack of 16 reads by the writer) */
                     fplh::format_batch_parallel(w->batch, w->res.data(), fmtThreads, w->outs, ffail ? &w->faileds : nullptr,
                                                 fragmentMode ? &w->frags : nullptr);
@@ -1336,6 +1370,8 @@ int main(int argc, char* argv[]) {
             cerr << "device thread " << d << ": " << nSubmit[d] << " submissions " << tSubmit[d] << " s (mean depth behind them "
                  << (nSubmit[d] ? (double)depthSum[d] / (double)nSubmit[d] : 0.0) << "), queue empty with room for a batch " << nMiss[d]
                  << " times, nothing in flight and nothing parsed " << tStarved[d] << " s" << endl;
+    if (cmd.exist("verbose") && devBamGz)
+        cerr << "device gzip: " << nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
     if (cmd.exist("verbose") && textMode) {
         if (devGz) cerr << "device gzip: " << nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
         cerr << "device parse: " << nTextBatches.load() << " chunks parsed on the device, " << nTextFallbacks.load()

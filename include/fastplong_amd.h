@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define FPL_ABI_VERSION 9
+#define FPL_ABI_VERSION 10
 
 /* limits */
 #define FPL_MAX_ADAPTER_LEN 255 /* longest adapter the device path accepts            */
@@ -369,7 +369,8 @@ int fpl_wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** re
  *                       valid until the next submission that takes this batch's slot.  A gzip batch may also be collected with
  *                       fpl_wait_text: its bytes are then never made.
  *                       Size: never more than 23 + n + 5 * (n / FPL_GZ_BLOCK_BYTES + 1 + 2 * fragments) bytes for n bytes of text.
- *   fpl_get_gzip_batches  how many batches fpl_wait_text_gz has made members for (the sibling of fpl_get_batch_forms).
+ *   fpl_get_gzip_batches  how many batches fpl_wait_text_gz (and, ABI v10, fpl_wait_bam_gz) has made members for (the sibling of
+ *                       fpl_get_batch_forms).
  */
 #define FPL_GZ_BLOCK_BYTES 16384
 int fpl_set_text_gzip(fpl_ctx* ctx, int on);
@@ -407,6 +408,33 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
                           uint32_t n_reads, uint8_t* seq_out, uint8_t* qual_out, fpl_read_result* results);
 int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off, uint32_t n_reads,
                    uint8_t* seq_out, uint8_t* qual_out);
+
+/*
+ * (ABI v10) The passing reads of a BAM batch as gzip, composed and deflated on the device: v8 and v9 joined.  Everything a member
+ * needs is in the batch's slot once fpl_process_bam_async has run -- the record bytes (the names), the decoded bases and
+ * qualities, the per-read records -- so a host that writes BAM input to a .gz neither formats nor deflates, and need not get the
+ * decoded arrays (2 bytes per base) back at all.
+ *
+ *   fpl_set_bam_gzip   a switch of the context, read by fpl_process_bam_async (the sibling of fpl_set_text_gzip): a BAM batch
+ *                      submitted while it is on is a GZIP batch.  Changes nothing about the batch's records, fragments or
+ *                      counters.  A gzip batch may pass seq_out == NULL && qual_out == NULL: the decoded arrays are then not
+ *                      copied back.  Both NULL or neither (FPL_ERR_ARG otherwise); with the switch off NULL stays FPL_ERR_ARG.
+ *                      Contexts with break_enabled / mask_enabled write from fragment lists: the switch is refused
+ *                      (FPL_ERR_STATE) for them.
+ *   fpl_wait_bam_gz    fpl_wait for the oldest batch in flight, plus its bytes: one complete gzip member whose inflation is, byte
+ *                      for byte, what the host's formatter appends to --out for the batch's FASTQ twin and `results` -- name
+ *                      line '@' + the record's read name (up to its NUL), the '+' line the one byte '+', and as for
+ *                      fpl_wait_text_gz every fragment with code FPL_PASS_FILTER of every read that was not dropped, in input
+ *                      order, the "split-by-adapter-left-" / "-right-" prefix behind the '@'.  Lifetime, the empty output
+ *                      (*gz_len 0 and *gz NULL: no read passed, or the batch is not a gzip batch -- a CSR batch or a BAM batch
+ *                      submitted with the switch off is collected exactly as by fpl_wait) and the way the member is made are
+ *                      those of fpl_wait_text_gz.  Size: never more than 23 + n + 5 * (n / FPL_GZ_BLOCK_BYTES + 1 + 2 *
+ *                      fragments) bytes for n bytes of text.  A gzip batch may also be collected with fpl_wait: its bytes are
+ *                      then never made.  A text batch at the head of the queue: FPL_ERR_STATE, as for fpl_wait.
+ * fpl_get_gzip_batches counts the members of both calls.
+ */
+int fpl_set_bam_gzip(fpl_ctx* ctx, int on);
+int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len);
 
 /* Page-locked host memory for the arrays handed to fpl_process_batch[_async] / fpl_process_text_async: the DMA engines read it
  * directly.  Blocks of 8 MB and more are anonymous memory on transparent huge pages, touched and registered with the runtime

@@ -276,6 +276,14 @@ int fpl_wait_text_gz(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result**
     *gz_len = 0;
     return fpl_wait_text(ctx, out, results, line_starts);
 }
+/* (ABI v10: BAM batches are refused above, so the switch is too -- a host keeps its own path -- and the wait is fpl_wait) */
+int fpl_set_bam_gzip(fpl_ctx* ctx, int on) { return !ctx ? FPL_ERR_ARG : on ? FPL_ERR_NO_DEVICE : FPL_OK; }
+int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
+    if (!gz || !gz_len) return FPL_ERR_ARG;
+    *gz = nullptr;
+    *gz_len = 0;
+    return fpl_wait(ctx);
+}
 int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return FPL_ERR_ARG;
     *out = 0;
