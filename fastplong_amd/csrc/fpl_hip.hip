@@ -19,11 +19,16 @@
 #include <vector>
 
 #include "pipeline.h"
+#include "buf.h"
 #include "text_parse.h"
 #include "gz_emit.h"
 #include "bam_decode.h"
 
 using namespace fpl;
+
+/* what a slot holds: a CSR batch (fpl_process_batch_async), a FASTQ text chunk (fpl_process_text_async) or BAM records
+   (fpl_process_bam_async).  fpl_wait / fpl_wait_bam_gz collect CSR and BAM batches, fpl_wait_text* text batches. */
+enum class BatchKind { CSR, Text, BAM };
 
 struct fpl_ctx {
     int device = -1;
@@ -32,40 +37,38 @@ struct fpl_ctx {
     bool probe_primed = false;
     int n_adapters = 2;
     u32 C = 0;
-    DevConfig* d_cfg = nullptr;
-    DevAdapter* d_ads = nullptr;
-    long long* d_counters = nullptr;
-    /* per-batch workspace, grown on demand */
-    u32 ws_reads = 0;
-    ReadState* d_state = nullptr;
-    ScanRec* d_recs = nullptr;  /* k_scan -> k_resolve */
-    ScanWin* d_wins = nullptr;
-    RedoItem* d_redo = nullptr; /* k_resolve -> k_redo */
-    uint64_t* d_frag_off = nullptr;
-    u32* d_frag_len = nullptr;
-    u32* d_work_ctr = nullptr;
-    /* --break / --mask (DevConfig::defer): lists k_break_mask appends to, sized per batch */
+    DevBuf<DevConfig> d_cfg;
+    DevBuf<DevAdapter> d_ads;
+    DevBuf<long long> d_counters;
+    /* per-batch workspace, grown on demand (ensure_workspace: all sized by the reads of the largest batch so far) */
+    DevBuf<ReadState> d_state;
+    DevBuf<ScanRec> d_recs;  /* k_scan -> k_resolve */
+    DevBuf<ScanWin> d_wins;
+    DevBuf<RedoItem> d_redo; /* k_resolve -> k_redo */
+    DevBuf<uint64_t> d_frag_off;
+    DevBuf<u32> d_frag_len;
+    DevBuf<u32> d_work_ctr;
+    /* --break / --mask (DevConfig::defer): lists k_break_mask appends to, sized per batch (ensure_break_mask; BmLists) */
     DevConfig hcfg;
-    u32* d_frag_cyc = nullptr;
-    BmLists bm = {nullptr, nullptr, 0, 0, 0, nullptr};
-    size_t scratch_slabs = 0;
-    u32* d_sort_ws = nullptr;       /* k_stats_sorted: bucket counters and the slice table */
-    size_t sort_ws_cap = 0;         /* words */
-    uint64_t* d_st_off = nullptr;   /* the reads in sorted order (ws_reads each) */
-    u32* d_st_len = nullptr;
-    u32* d_st_e = nullptr;
-    u64* d_stats_scratch = nullptr;
-    u8* d_stats_flags = nullptr;
-    u64* d_extra_scratch = nullptr; /* the post-only pass's own slabs / flags (it runs on s_aux beside the reduce of k_stats_sorted) */
-    u8* d_extra_flags = nullptr;
-    size_t extra_slabs = 0;
+    DevBuf<u32> d_frag_cyc;
+    DevBuf<fpl_fragment> d_bm_frags;
+    DevBuf<fpl_region> d_bm_regs;
+    DevBuf<u32> d_bm_counts;
+    DevBuf<u32> d_sort_ws;       /* k_stats_sorted: bucket counters and the slice table (words) */
+    DevBuf<uint64_t> d_st_off;   /* the reads in sorted order (as many as d_state) */
+    DevBuf<u32> d_st_len;
+    DevBuf<u32> d_st_e;
+    DevBuf<u64> d_stats_scratch; /* slabs of FS_SLAB words; beside them two flag bytes per slab + 64 */
+    DevBuf<u8> d_stats_flags;
+    DevBuf<u64> d_extra_scratch; /* the post-only pass's own slabs / flags (it runs on s_aux beside the reduce of k_stats_sorted) */
+    DevBuf<u8> d_extra_flags;
     /* The end trims of batch k + 1 beside the kernels of batch k ("trim ahead"): the trim kernel is the first of a batch, needs
        nothing of the batch before, and is bound by memory latency where k_scan / k_stats_sorted are bound by instruction issue
        -- 0.5 ms of a 12.5 ms step when two whole batches run side by side (round 4, tools/overlap_probe.py).  It writes
        ReadState[] and takes its groups off a work counter: both exist twice, batches alternate.  A batch qualifies when its
        inputs are known to be complete on the device before its predecessor is done: the asynchronous path (its own H2D
        event), or a caller's promise (fpl_assume_inputs_ready). */
-    ReadState* d_state2 = nullptr;
+    DevBuf<ReadState> d_state2;
     hipStream_t s_trim = nullptr;
     hipEvent_t ev_trim_done = nullptr, ev_batch_done[2] = {nullptr, nullptr}, ev_stats_done[2] = {nullptr, nullptr};
     int ahead_gate = 0;             /* FPL_TRIM_AHEAD_GATE: 0 the trims of batch k + 1 start as soon as batch k - 1 is done -- beside k_scan of
@@ -81,67 +84,57 @@ struct fpl_ctx {
     /* staging for the host-pointer entry points: FPL_MAX_IN_FLIGHT slots, so that the copies of one batch
        overlap the kernels of the previous one */
     struct Slot {
-        uint64_t st_bytes = 0;
-        u32 st_reads = 0;
-        u32 h_res_cap = 0; /* records h_results holds (a text slot sizes it by the records its chunk really has) */
-        u8* d_seq = nullptr;
-        u8* d_qual = nullptr;
-        uint64_t* d_off = nullptr;
-        fpl_read_result* d_results = nullptr;
-        fpl_read_result* h_results = nullptr; /* pinned: the D2H copy never waits for a pageable destination */
-        u32 h_reads = 0;
+        BatchKind kind = BatchKind::CSR;
+        bool gz = false; /* a text or BAM batch whose passing reads also come back as a gzip member (`gzip` below) */
+        /* every kind: the reads as CSR arrays on the device (uploaded, parsed out of the text or decoded from the BAM records),
+           their records there and in page-locked memory (the D2H copy never waits for a pageable destination; a text slot
+           sizes h_results by the records its chunk really has) */
+        DevBuf<u8> d_seq, d_qual;
+        DevBuf<uint64_t> d_off;
+        DevBuf<fpl_read_result> d_results;
+        PinBuf<fpl_read_result> h_results;
         hipEvent_t ev_h2d = nullptr, ev_kern = nullptr, ev_done = nullptr;
+        hipEvent_t ev_parsed = nullptr; /* text: the parse is done and the header is in; BAM: the bases are decoded */
         fpl_read_result* user_results = nullptr;
         u32 n_reads = 0;
-        int rc = FPL_OK; /* error met while enqueueing, reported by fpl_wait */
-        /* a TEXT batch (fpl_process_text_async): the chunk's bytes, its line breaks, the records' line starts and lengths; stage 1
-           (copy + parse + the header's way back) is enqueued at submission, stage 2 (the per-read kernels, the records' and line
-           starts' way back) once the header is in -- by the next submission or by the wait, whichever comes first */
-        int kind = 0;          /* 0 CSR batch, 1 text batch */
-        bool cancelled = false; /* text: fpl_cancel_text -- never run, reported by its wait */
-        int stage = 0;         /* text: 1 parse enqueued, 2 batch enqueued (or nothing to enqueue) */
-        uint64_t text_cap = 0; /* bytes d_text holds */
-        u32 rec_cap = 0;       /* records d_line / d_len / h_line hold */
-        u8* d_text = nullptr;
-        u32* d_nl = nullptr;
-        u32* d_blk = nullptr;
-        u32* d_line = nullptr;
-        u32* d_len = nullptr;
-        TextHeader* d_hdr = nullptr;
-        TextHeader* h_hdr = nullptr; /* pinned */
-        u32* h_line = nullptr;       /* pinned */
-        u32 h_line_cap = 0;
-        uint64_t text_bytes = 0;
-        hipEvent_t ev_parsed = nullptr;
-        /* a GZIP batch (fpl_set_text_gzip; csrc/gz_emit.h): a text batch whose passing reads also come back as a gzip member.  The
-           layout is enqueued behind the per-read kernels (text_continue); everything behind it is sized by what the layout
-           found and enqueued by fpl_wait_text_gz */
-        bool gz = false;
-        u32 gz_rec_cap = 0, gz_blk_cap = 0; /* entries d_rec_off / the d_gz_blk_* arrays hold */
-        u64* d_rec_off = nullptr;
-        u64* d_gz_blk_start = nullptr;
-        u64* d_gz_blk_off = nullptr;
-        u32* d_gz_blk_size = nullptr;
-        u32* d_gz_blk_crc = nullptr;
-        GzHeader* d_gz_hdr = nullptr;
-        GzHeader* h_gz_hdr = nullptr; /* pinned */
-        u8* d_gz_comp = nullptr;      /* the composed text */
-        u8* d_gz_tmp = nullptr;       /* every deflate block in a slot of its own */
-        u8* d_gz_out = nullptr;       /* the member */
-        uint64_t gz_comp_cap = 0, gz_out_cap = 0;
-        u8* h_gz = nullptr; /* pinned */
-        uint64_t h_gz_cap = 0;
-        hipEvent_t ev_gz = nullptr;
-        /* a BAM batch (fpl_process_bam_async): the inflated record bytes and where every record starts; a CSR batch otherwise.
-           bam_gz: a gzip BAM batch (fpl_set_bam_gzip) -- `gz` above with the BAM forms of the layout and compose kernels, which
-           read d_bam / d_rec / d_seq / d_qual / d_off / d_results of THIS slot: nothing touches them before the slot's next
-           submission, which comes after its wait */
-        bool bam_gz = false;
-        uint64_t bam_bases = 0;
-        u8* d_bam = nullptr;
-        uint64_t bam_cap = 0;
-        uint64_t* d_rec = nullptr;
-        u32 rec_st_cap = 0;
+        int rc = FPL_OK; /* error met while enqueueing, reported by the slot's wait */
+        /* a TEXT batch: the chunk's bytes, its line breaks, the records' line starts and lengths; stage 1 (copy + parse + the
+           header's way back) is enqueued at submission, stage 2 (the per-read kernels, the records' and line starts' way back) once
+           the header is in -- by fpl_start_text or by the wait, whichever comes first */
+        struct Text {
+            bool cancelled = false; /* fpl_cancel_text -- never run, reported by its wait */
+            int stage = 0;          /* 1 parse enqueued, 2 batch enqueued (or nothing to enqueue) */
+            uint64_t bytes = 0;
+            DevBuf<u8> d_text;      /* the chunk and 16 bytes of padding */
+            DevBuf<u32> d_nl, d_blk, d_line, d_len;
+            DevBuf<TextHeader> d_hdr;
+            PinBuf<TextHeader> h_hdr;
+            PinBuf<u32> h_line;     /* four line starts per record */
+        } text;
+        /* a GZIP batch (fpl_set_text_gzip / fpl_set_bam_gzip; csrc/gz_emit.h).  The layout is enqueued behind the per-read kernels
+           (submit_tail); everything behind it is sized by what the layout found and enqueued by the wait (gz_emit).  The BAM forms
+           of the layout and compose kernels read d_bam / d_rec / d_seq / d_qual / d_off / d_results of THIS slot: nothing touches
+           them before the slot's next submission, which comes after its wait */
+        struct Gzip {
+            DevBuf<u64> d_rec_off;
+            DevBuf<u64> d_blk_start, d_blk_off;
+            DevBuf<u32> d_blk_size, d_blk_crc;
+            DevBuf<GzHeader> d_hdr;
+            PinBuf<GzHeader> h_hdr;
+            DevBuf<u8> d_comp; /* the composed text */
+            DevBuf<u8> d_tmp;  /* every deflate block in a slot of its own */
+            DevBuf<u8> d_out;  /* the member */
+            PinBuf<u8> h_out;
+            hipEvent_t ev = nullptr;
+        } gzip;
+        /* a BAM batch: the inflated record bytes, where every record starts, and where the decoded bases go on the host (NULL: a
+           gzip batch that leaves them on the device) */
+        struct Bam {
+            uint64_t o_begin = 0, bases = 0;
+            uint8_t *seq_out = nullptr, *qual_out = nullptr;
+            DevBuf<u8> d_bam;
+            DevBuf<uint64_t> d_rec;
+        } bam;
     };
     Slot slot[FPL_MAX_IN_FLIGHT];
     u32 submitted = 0, waited = 0; /* batches handed to / collected from the asynchronous path */
@@ -213,10 +206,10 @@ void fpl_options_default(fpl_options* o) {
     o->mask_quality = 10;
 }
 
-static int alloc_counters(fpl_ctx* ctx, u32 C, long long** out) {
+static int alloc_counters(fpl_ctx* ctx, u32 C, DevBuf<long long>& out) {
     size_t n = FPL_COUNTERS_LEN(C, ctx->n_adapters);
-    FPL_HIP(hipMalloc((void**)out, n * sizeof(long long)));
-    FPL_HIP(hipMemset(*out, 0, n * sizeof(long long)));
+    FPL_HIP(out.alloc(n));
+    FPL_HIP(hipMemset(out.ptr, 0, n * sizeof(long long)));
     return FPL_OK;
 }
 
@@ -268,7 +261,7 @@ int fpl_create(fpl_ctx** out, const fpl_options* opt, const char* start_adapter,
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_kern, hipEventDisableTiming));
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_parsed, hipEventDisableTiming));
-            FPL_HIP(hipEventCreateWithFlags(&sl.ev_gz, hipEventDisableTiming));
+            FPL_HIP(hipEventCreateWithFlags(&sl.gzip.ev, hipEventDisableTiming));
         }
         DevConfig cfg;
         build_config(&cfg, opt, start_len, end_len, n_fasta);
@@ -291,13 +284,13 @@ int fpl_create(fpl_ctx** out, const fpl_options* opt, const char* start_adapter,
             return FPL_ERR_ARG; /* (the caller below destroys the context) */
         }
         ctx->hcfg = cfg;
-        FPL_HIP(hipMalloc((void**)&ctx->d_cfg, sizeof(DevConfig)));
-        FPL_HIP(hipMemcpy(ctx->d_cfg, &cfg, sizeof(cfg), hipMemcpyHostToDevice));
-        FPL_HIP(hipMalloc((void**)&ctx->d_ads, sizeof(DevAdapter) * ads.size()));
-        FPL_HIP(hipMemcpy(ctx->d_ads, ads.data(), sizeof(DevAdapter) * ads.size(), hipMemcpyHostToDevice));
-        FPL_HIP(hipMalloc((void**)&ctx->d_work_ctr, 2 * WORK_CTR_WORDS * sizeof(u32))); /* (two sets: batches alternate) */
+        FPL_HIP(ctx->d_cfg.alloc(1));
+        FPL_HIP(hipMemcpy(ctx->d_cfg.ptr, &cfg, sizeof(cfg), hipMemcpyHostToDevice));
+        FPL_HIP(ctx->d_ads.alloc(ads.size()));
+        FPL_HIP(hipMemcpy(ctx->d_ads.ptr, ads.data(), sizeof(DevAdapter) * ads.size(), hipMemcpyHostToDevice));
+        FPL_HIP(ctx->d_work_ctr.alloc(2 * WORK_CTR_WORDS)); /* (two sets: batches alternate) */
         ctx->C = max_cycles ? max_cycles : 1;
-        int r = alloc_counters(ctx, ctx->C, &ctx->d_counters);
+        int r = alloc_counters(ctx, ctx->C, ctx->d_counters);
         if (r != FPL_OK) return r;
         /* (the ring of timing events -- a thousand of them -- is made when timing is first asked for: a command-line run never does) */
         return FPL_OK;
@@ -315,24 +308,9 @@ void fpl_destroy(fpl_ctx* ctx) {
     if (!ctx) return;
     if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    void* ptrs[] = {ctx->d_cfg, ctx->d_ads, ctx->d_counters, ctx->d_state, ctx->d_frag_off, ctx->d_frag_len,
-                    ctx->d_work_ctr, ctx->d_stats_scratch, ctx->d_extra_scratch, ctx->d_extra_flags,
-                    ctx->d_stats_flags, ctx->d_frag_cyc, ctx->bm.frags, ctx->bm.regs, ctx->bm.counts,
-                    ctx->d_sort_ws, ctx->d_st_off, ctx->d_st_len, ctx->d_st_e, ctx->d_recs, ctx->d_redo, ctx->d_wins};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    /* (the buffers of the context and of its slots go with the `delete` below) */
     for (auto& sl : ctx->slot) {
-        void* sp[] = {sl.d_seq, sl.d_qual, sl.d_off, sl.d_results, sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len, sl.d_hdr, sl.d_bam, sl.d_rec,
-                      sl.d_rec_off, sl.d_gz_blk_start, sl.d_gz_blk_off, sl.d_gz_blk_size, sl.d_gz_blk_crc, sl.d_gz_hdr, sl.d_gz_comp,
-                      sl.d_gz_tmp, sl.d_gz_out};
-        for (void* p : sp)
-            if (p) (void)hipFree(p);
-        if (sl.h_results) (void)hipHostFree(sl.h_results);
-        if (sl.h_hdr) (void)hipHostFree(sl.h_hdr);
-        if (sl.h_line) (void)hipHostFree(sl.h_line);
-        if (sl.h_gz_hdr) (void)hipHostFree(sl.h_gz_hdr);
-        if (sl.h_gz) (void)hipHostFree(sl.h_gz);
-        if (sl.ev_gz) (void)hipEventDestroy(sl.ev_gz);
+        if (sl.gzip.ev) (void)hipEventDestroy(sl.gzip.ev);
         if (sl.ev_parsed) (void)hipEventDestroy(sl.ev_parsed);
         if (sl.ev_h2d) (void)hipEventDestroy(sl.ev_h2d);
         if (sl.ev_kern) (void)hipEventDestroy(sl.ev_kern);
@@ -348,7 +326,6 @@ void fpl_destroy(fpl_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_stats_done)
         if (e) (void)hipEventDestroy(e);
-    if (ctx->d_state2) (void)hipFree(ctx->d_state2);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     for (int r = 0; r < fpl_ctx::EV_RING; r++)
@@ -361,7 +338,7 @@ void fpl_destroy(fpl_ctx* ctx) {
 uint32_t fpl_max_cycles(const fpl_ctx* ctx) { return ctx ? ctx->C : 0; }
 int32_t fpl_n_adapters(const fpl_ctx* ctx) { return ctx ? ctx->n_adapters : 0; }
 size_t fpl_counters_len(const fpl_ctx* ctx) { return ctx ? FPL_COUNTERS_LEN(ctx->C, ctx->n_adapters) : 0; }
-void* fpl_counters_device_ptr(fpl_ctx* ctx) { return ctx ? ctx->d_counters : nullptr; }
+void* fpl_counters_device_ptr(fpl_ctx* ctx) { return ctx ? ctx->d_counters.ptr : nullptr; }
 
 int fpl_synchronize(fpl_ctx* ctx) {
     if (!ctx) return FPL_ERR_ARG;
@@ -376,21 +353,20 @@ int fpl_reserve_cycles(fpl_ctx* ctx, uint32_t max_cycles) {
     if (max_cycles <= ctx->C) return FPL_OK;
     FPL_HIP(hipSetDevice(ctx->device));
     FPL_HIP(hipDeviceSynchronize());
-    long long* nw = nullptr;
+    DevBuf<long long> nw;
     const u32 Co = ctx->C, Cn = max_cycles;
-    int r = alloc_counters(ctx, Cn, &nw);
+    int r = alloc_counters(ctx, Cn, nw);
     if (r != FPL_OK) return r;
     for (int k = 0; k < 2; k++) {
-        const long long* so = ctx->d_counters + (size_t)k * FPL_STATS_LEN(Co);
-        long long* sn = nw + (size_t)k * FPL_STATS_LEN(Cn);
+        const long long* so = ctx->d_counters.ptr + (size_t)k * FPL_STATS_LEN(Co);
+        long long* sn = nw.ptr + (size_t)k * FPL_STATS_LEN(Cn);
         FPL_HIP(hipMemcpy(sn, so, (size_t)Co * FPL_CYC_STRIDE * sizeof(long long), hipMemcpyDeviceToDevice));
         FPL_HIP(hipMemcpy(sn + (size_t)Cn * FPL_CYC_STRIDE, so + (size_t)Co * FPL_CYC_STRIDE,
                           FPL_STATS_TAIL * sizeof(long long), hipMemcpyDeviceToDevice));
     }
-    FPL_HIP(hipMemcpy(nw + FPL_OFF_FR(Cn), ctx->d_counters + FPL_OFF_FR(Co),
+    FPL_HIP(hipMemcpy(nw.ptr + FPL_OFF_FR(Cn), ctx->d_counters.ptr + FPL_OFF_FR(Co),
                       (FPL_FR_LEN + FPL_KEYHIST_LEN(ctx->n_adapters)) * sizeof(long long), hipMemcpyDeviceToDevice));
-    FPL_HIP(hipFree(ctx->d_counters));
-    ctx->d_counters = nw;
+    ctx->d_counters.swap(nw); /* (the old block goes with nw) */
     ctx->C = Cn;
     return FPL_OK;
 }
@@ -399,7 +375,7 @@ int fpl_get_counters(fpl_ctx* ctx, int64_t* host_buf, size_t n) {
     if (!ctx || !host_buf || n != fpl_counters_len(ctx)) return FPL_ERR_ARG;
     FPL_HIP(hipSetDevice(ctx->device));
     FPL_HIP(hipDeviceSynchronize());
-    FPL_HIP(hipMemcpy(host_buf, ctx->d_counters, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    FPL_HIP(hipMemcpy(host_buf, ctx->d_counters.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
     return FPL_OK;
 }
 
@@ -579,7 +555,7 @@ int fpl_allreduce_counters(fpl_ctx** ctxs, int32_t n) {
             rc = FPL_ERR_HIP;
             break;
         }
-        FPL_NCCL(g_rccl.AllReduce(ctxs[i]->d_counters, ctxs[i]->d_counters, len, ncclInt64, ncclSum, comms[(size_t)i], ctxs[i]->s_aux));
+        FPL_NCCL(g_rccl.AllReduce(ctxs[i]->d_counters.ptr, ctxs[i]->d_counters.ptr, len, ncclInt64, ncclSum, comms[(size_t)i], ctxs[i]->s_aux));
     }
     FPL_NCCL(g_rccl.GroupEnd());
     for (int i = 0; i < n; i++) {
@@ -626,23 +602,17 @@ int fpl_reset_counters(fpl_ctx* ctx) {
     ctx->gz_batches = 0;
     FPL_HIP(hipSetDevice(ctx->device));
     FPL_HIP(hipDeviceSynchronize());
-    FPL_HIP(hipMemset(ctx->d_counters, 0, fpl_counters_len(ctx) * sizeof(long long)));
+    FPL_HIP(hipMemset(ctx->d_counters.ptr, 0, fpl_counters_len(ctx) * sizeof(long long)));
     return FPL_OK;
 }
 
+/* (every ensure_*: a group sized by one number grows together behind one device-wide wait, with a quarter of headroom) */
 static int ensure_scratch(fpl_ctx* ctx, u32 n_reads, uint64_t n_bytes, u32 max_read_len) {
     const size_t slabs = stats_scratch_slabs(n_reads, n_bytes, max_read_len, ctx->n_cu, ctx->tune);
-    if (slabs <= ctx->scratch_slabs) return FPL_OK;
-    FPL_HIP(hipDeviceSynchronize());
-    if (ctx->d_stats_scratch) (void)hipFree(ctx->d_stats_scratch);
-    if (ctx->d_stats_flags) (void)hipFree(ctx->d_stats_flags);
-    ctx->d_stats_scratch = nullptr;
-    ctx->d_stats_flags = nullptr;
-    ctx->scratch_slabs = 0;
-    const size_t cap = slabs + slabs / 4;
-    FPL_HIP(hipMalloc((void**)&ctx->d_stats_scratch, cap * (size_t)FS_SLAB * sizeof(u64)));
-    FPL_HIP(hipMalloc((void**)&ctx->d_stats_flags, 2 * cap + 64)); /* slab flags + tile flags: tiles <= slabs, whatever the shape */
-    ctx->scratch_slabs = cap;
+    if (ctx->d_stats_scratch.holds(slabs * (size_t)FS_SLAB)) return FPL_OK;
+    const size_t cap = grown(slabs, 0);
+    FPL_HIP(regrow(ctx->d_stats_scratch.want(cap * (size_t)FS_SLAB),
+                   ctx->d_stats_flags.want(2 * cap + 64))); /* slab flags + tile flags: tiles <= slabs, whatever the shape */
     return FPL_OK;
 }
 
@@ -653,111 +623,48 @@ static int ensure_extra_scratch(fpl_ctx* ctx, u32 n_reads, u32 max_read_len, boo
     if (!sorted) return FPL_OK;
     const u32 n_tiles = cdiv(max_read_len ? max_read_len : 1, FS_T);
     const size_t slabs = (size_t)stats_extra_blocks(n_reads, ctx->tune) * n_tiles;
-    if (slabs <= ctx->extra_slabs) return FPL_OK;
-    FPL_HIP(hipDeviceSynchronize());
-    if (ctx->d_extra_scratch) (void)hipFree(ctx->d_extra_scratch);
-    if (ctx->d_extra_flags) (void)hipFree(ctx->d_extra_flags);
-    ctx->d_extra_scratch = nullptr;
-    ctx->d_extra_flags = nullptr;
-    ctx->extra_slabs = 0;
-    const size_t cap = slabs + slabs / 4;
-    FPL_HIP(hipMalloc((void**)&ctx->d_extra_scratch, cap * (size_t)FS_SLAB * sizeof(u64)));
-    FPL_HIP(hipMalloc((void**)&ctx->d_extra_flags, 2 * cap + 64)); /* (slab flags + tile flags) */
-    ctx->extra_slabs = cap;
+    if (ctx->d_extra_scratch.holds(slabs * (size_t)FS_SLAB)) return FPL_OK;
+    const size_t cap = grown(slabs, 0);
+    FPL_HIP(regrow(ctx->d_extra_scratch.want(cap * (size_t)FS_SLAB), ctx->d_extra_flags.want(2 * cap + 64))); /* (slab flags + tile flags) */
     return FPL_OK;
 }
 
 static int ensure_sort_ws(fpl_ctx* ctx, u32 n_reads, uint64_t n_bytes) {
     const u32 per = stats_items_per_slice(n_reads, n_reads ? (u32)(n_bytes / n_reads) : 0, ctx->n_cu, ctx->tune);
-    const size_t words = sort_ws_words(stats_sorted_max_slices(n_reads, per, ctx->tune), n_reads);
-    if (words <= ctx->sort_ws_cap) return FPL_OK;
-    FPL_HIP(hipDeviceSynchronize());
-    if (ctx->d_sort_ws) (void)hipFree(ctx->d_sort_ws);
-    ctx->d_sort_ws = nullptr;
-    ctx->sort_ws_cap = 0;
-    const size_t cap = words + words / 4;
-    FPL_HIP(hipMalloc((void**)&ctx->d_sort_ws, cap * sizeof(u32)));
-    ctx->sort_ws_cap = cap;
+    FPL_HIP(ctx->d_sort_ws.grow(sort_ws_words(stats_sorted_max_slices(n_reads, per, ctx->tune), n_reads), 0));
     return FPL_OK;
 }
 
-/* the fragment / region / piece lists of k_break_mask: capacities grow (25 % headroom) and never shrink, so that a
-   run whose batches differ a little in size does not reallocate -- and wait for the device -- on every batch */
+/* the fragment / region / piece lists of k_break_mask: capacities grow (25 % headroom) and never shrink -- when one list is too
+   small all are made anew, none below what it had --, so that a run whose batches differ a little in size does not reallocate
+   -- and wait for the device -- on every batch */
 static int ensure_break_mask(fpl_ctx* ctx, u32 n_reads, uint64_t n_bytes) {
     if (!ctx->hcfg.defer) return FPL_OK;
-    if (!ctx->bm.counts) FPL_HIP(hipMalloc((void**)&ctx->bm.counts, 4 * sizeof(u32)));
+    if (!ctx->d_bm_counts.ptr) FPL_HIP(ctx->d_bm_counts.alloc(4));
     u32 need_f = 0, need_r = 0, need_i = 0;
     break_mask_caps(n_reads, n_bytes, ctx->hcfg.brk, ctx->hcfg.brk_w, ctx->hcfg.msk, ctx->hcfg.msk_w, need_f, need_r, need_i);
-    if (ctx->bm.frags && need_f <= ctx->bm.frag_cap && need_r <= ctx->bm.reg_cap && need_i <= ctx->bm.item_cap) return FPL_OK;
-    FPL_HIP(hipDeviceSynchronize());
-    if (ctx->bm.frags) (void)hipFree(ctx->bm.frags);
-    if (ctx->bm.regs) (void)hipFree(ctx->bm.regs);
-    if (ctx->d_frag_cyc) (void)hipFree(ctx->d_frag_cyc);
-    if (ctx->d_frag_off) (void)hipFree(ctx->d_frag_off);
-    if (ctx->d_frag_len) (void)hipFree(ctx->d_frag_len);
-    ctx->bm.frags = nullptr;
-    ctx->bm.regs = nullptr;
-    ctx->d_frag_cyc = nullptr;
-    ctx->d_frag_off = nullptr;
-    ctx->d_frag_len = nullptr;
-    auto grow = [](u32 have, u32 need) -> u32 {
-        const uint64_t want = (uint64_t)need + need / 4 + 64;
-        const uint64_t cap = want < 0x7FFFFFF0ull ? want : 0x7FFFFFF0ull;
-        return have > cap ? have : (u32)cap;
-    };
-    ctx->bm.frag_cap = grow(ctx->bm.frag_cap, need_f);
-    ctx->bm.reg_cap = grow(ctx->bm.reg_cap, need_r);
-    ctx->bm.item_cap = grow(ctx->bm.item_cap, need_i);
-    FPL_HIP(hipMalloc((void**)&ctx->bm.frags, sizeof(fpl_fragment) * (size_t)ctx->bm.frag_cap));
-    FPL_HIP(hipMalloc((void**)&ctx->bm.regs, sizeof(fpl_region) * (size_t)ctx->bm.reg_cap));
-    FPL_HIP(hipMalloc((void**)&ctx->d_frag_off, sizeof(uint64_t) * (size_t)ctx->bm.item_cap));
-    FPL_HIP(hipMalloc((void**)&ctx->d_frag_len, sizeof(u32) * (size_t)ctx->bm.item_cap));
-    FPL_HIP(hipMalloc((void**)&ctx->d_frag_cyc, sizeof(u32) * (size_t)ctx->bm.item_cap));
+    if (ctx->d_bm_frags.holds(need_f) && need_r <= ctx->d_bm_regs.cap && need_i <= ctx->d_frag_cyc.cap) return FPL_OK;
+    const size_t frag_cap = std::max(ctx->d_bm_frags.cap, grown(need_f, 64, 0x7FFFFFF0u));
+    const size_t reg_cap = std::max(ctx->d_bm_regs.cap, grown(need_r, 64, 0x7FFFFFF0u));
+    const size_t item_cap = std::max(ctx->d_frag_cyc.cap, grown(need_i, 64, 0x7FFFFFF0u));
+    FPL_HIP(regrow(ctx->d_bm_frags.want(frag_cap), ctx->d_bm_regs.want(reg_cap), ctx->d_frag_off.want(item_cap),
+                   ctx->d_frag_len.want(item_cap), ctx->d_frag_cyc.want(item_cap)));
     return FPL_OK;
 }
 
 static int ensure_workspace(fpl_ctx* ctx, u32 n_reads) {
-    if (n_reads <= ctx->ws_reads) return FPL_OK;
+    if (ctx->d_state.holds(n_reads)) return FPL_OK;
     /* 25 % headroom, as the other workspaces: a host that cuts its input by BYTES hands in batches whose read counts wander by a few
        per cent, and every new record used to cost a device-wide wait, a dozen hipFree and as many hipMalloc -- 3 to 9 ms each, five or
        six times in the first 60 ms of a run (rocprofv3 timeline of the CLI, tools/cli_timeline.sh) */
-    {
-        const uint64_t want = (uint64_t)n_reads + n_reads / 4 + 1024;
-        n_reads = want > 0xFFFFFFF0ull ? n_reads : (u32)want;
-    }
-    FPL_HIP(hipDeviceSynchronize());
-    if (ctx->d_state) (void)hipFree(ctx->d_state);
-    if (ctx->d_state2) (void)hipFree(ctx->d_state2);
-    ctx->d_state = ctx->d_state2 = nullptr;
-    ctx->ws_reads = 0;
-    FPL_HIP(hipMalloc((void**)&ctx->d_state, sizeof(ReadState) * (size_t)n_reads));
-    FPL_HIP(hipMalloc((void**)&ctx->d_state2, sizeof(ReadState) * (size_t)n_reads));
-    if (ctx->d_recs) (void)hipFree(ctx->d_recs);
-    if (ctx->d_redo) (void)hipFree(ctx->d_redo);
-    if (ctx->d_wins) (void)hipFree(ctx->d_wins);
-    ctx->d_recs = nullptr;
-    ctx->d_redo = nullptr;
-    ctx->d_wins = nullptr;
-    FPL_HIP(hipMalloc((void**)&ctx->d_wins, sizeof(ScanWin) * (size_t)n_reads));
-    FPL_HIP(hipMalloc((void**)&ctx->d_recs, sizeof(ScanRec) * (size_t)n_reads));
-    FPL_HIP(hipMalloc((void**)&ctx->d_redo, sizeof(RedoItem) * (size_t)n_reads));
-    if (ctx->d_st_off) (void)hipFree(ctx->d_st_off);
-    if (ctx->d_st_len) (void)hipFree(ctx->d_st_len);
-    if (ctx->d_st_e) (void)hipFree(ctx->d_st_e);
-    ctx->d_st_off = nullptr;
-    ctx->d_st_len = ctx->d_st_e = nullptr;
-    FPL_HIP(hipMalloc((void**)&ctx->d_st_off, sizeof(uint64_t) * (size_t)n_reads));
-    FPL_HIP(hipMalloc((void**)&ctx->d_st_len, sizeof(u32) * (size_t)n_reads));
-    FPL_HIP(hipMalloc((void**)&ctx->d_st_e, sizeof(u32) * (size_t)n_reads));
-    if (!ctx->hcfg.defer) { /* (with --break / --mask the item list is sized by ensure_break_mask) */
-        if (ctx->d_frag_off) (void)hipFree(ctx->d_frag_off);
-        if (ctx->d_frag_len) (void)hipFree(ctx->d_frag_len);
-        ctx->d_frag_off = nullptr;
-        ctx->d_frag_len = nullptr;
-        FPL_HIP(hipMalloc((void**)&ctx->d_frag_off, sizeof(uint64_t) * 2 * (size_t)n_reads));
-        FPL_HIP(hipMalloc((void**)&ctx->d_frag_len, sizeof(u32) * 2 * (size_t)n_reads));
-    }
-    ctx->ws_reads = n_reads;
+    const size_t cap = grown(n_reads, 1024);
+    if (ctx->hcfg.defer) /* (with --break / --mask the item list is sized by ensure_break_mask) */
+        FPL_HIP(regrow(ctx->d_state.want(cap), ctx->d_state2.want(cap), ctx->d_wins.want(cap), ctx->d_recs.want(cap), ctx->d_redo.want(cap),
+                       ctx->d_st_off.want(cap), ctx->d_st_len.want(cap), ctx->d_st_e.want(cap)));
+    else
+        FPL_HIP(regrow(ctx->d_state.want(cap), ctx->d_state2.want(cap), ctx->d_wins.want(cap), ctx->d_recs.want(cap), ctx->d_redo.want(cap),
+                       ctx->d_st_off.want(cap), ctx->d_st_len.want(cap), ctx->d_st_e.want(cap), ctx->d_frag_off.want(2 * cap),
+                       ctx->d_frag_len.want(2 * cap)));
     return FPL_OK;
 }
 
@@ -793,7 +700,7 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
     }
     /* which of the two ReadState[] / work-counter sets this batch takes, and whether its end trims start ahead of the main stream */
     const int par = (int)(ctx->batch_no & 1);
-    u32* const work_ctr = ctx->d_work_ctr + par * WORK_CTR_WORDS;
+    u32* const work_ctr = ctx->d_work_ctr.ptr + par * WORK_CTR_WORDS;
     hipEvent_t inputs_ev = ctx->next_inputs_event;
     ctx->next_inputs_event = nullptr;
     const bool ahead = n_reads && ctx->trim_ahead && ctx->overlap && !ctx->dbg && !ctx->hcfg.defer && ctx->batch_no > 0 &&
@@ -809,7 +716,7 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
             FPL_HIP(hipMemsetAsync(work_ctr, 0, WORK_CTR_WORDS * sizeof(u32), stream));
         }
     }
-    if (ctx->hcfg.defer && ctx->bm.counts) FPL_HIP(hipMemsetAsync(ctx->bm.counts, 0, 4 * sizeof(u32), stream));
+    if (ctx->hcfg.defer && ctx->d_bm_counts.ptr) FPL_HIP(hipMemsetAsync(ctx->d_bm_counts.ptr, 0, 4 * sizeof(u32), stream));
     BatchArgs a;
     a.seq = d_seq;
     a.qual = d_qual;
@@ -817,38 +724,39 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
     a.n_reads = n_reads;
     a.n_bytes = n_bytes;
     a.max_read_len = max_read_len;
-    a.cfg = ctx->d_cfg;
-    a.ads = ctx->d_ads;
-    a.state = par ? ctx->d_state2 : ctx->d_state;
+    a.cfg = ctx->d_cfg.ptr;
+    a.ads = ctx->d_ads.ptr;
+    a.state = par ? ctx->d_state2.ptr : ctx->d_state.ptr;
     if (ctx->trim_ahead && ctx->overlap) a.ev_stats_done = (void*)ctx->ev_stats_done[par];
     if (ahead) {
         a.trim_stream = ctx->s_trim;
         a.ev_trim_done = (void*)ctx->ev_trim_done;
     }
     a.results = d_results;
-    a.frag_off = ctx->d_frag_off;
-    a.frag_len = ctx->d_frag_len;
-    a.frag_cyc = ctx->d_frag_cyc;
-    a.bm = ctx->bm;
+    a.frag_off = ctx->d_frag_off.ptr;
+    a.frag_len = ctx->d_frag_len.ptr;
+    a.frag_cyc = ctx->d_frag_cyc.ptr;
+    a.bm = BmLists{ctx->d_bm_frags.ptr, ctx->d_bm_regs.ptr, (u32)ctx->d_bm_frags.cap, (u32)ctx->d_bm_regs.cap, (u32)ctx->d_frag_cyc.cap,
+                     ctx->d_bm_counts.ptr};
     a.defer = ctx->hcfg.defer != 0;
     a.trim_mode = ctx->hcfg.trim_mode;
     a.n_fasta = ctx->hcfg.n_fasta;
     a.scan_short = ctx->hcfg.scan_short != 0;
-    a.counters = ctx->d_counters;
+    a.counters = ctx->d_counters.ptr;
     a.C = ctx->C;
     a.work_ctr = work_ctr;
-    a.recs = ctx->d_recs;
-    a.wins = ctx->d_wins;
-    a.redo = ctx->d_redo;
-    a.sort_ws = ctx->d_sort_ws;
-    a.st_off = ctx->d_st_off;
-    a.st_len = ctx->d_st_len;
-    a.st_e = ctx->d_st_e;
-    a.stats_scratch = ctx->d_stats_scratch;
-    a.stats_flags = ctx->d_stats_flags;
-    if (ctx->overlap && ctx->d_extra_scratch) {
-        a.extra_scratch = ctx->d_extra_scratch;
-        a.extra_flags = ctx->d_extra_flags;
+    a.recs = ctx->d_recs.ptr;
+    a.wins = ctx->d_wins.ptr;
+    a.redo = ctx->d_redo.ptr;
+    a.sort_ws = ctx->d_sort_ws.ptr;
+    a.st_off = ctx->d_st_off.ptr;
+    a.st_len = ctx->d_st_len.ptr;
+    a.st_e = ctx->d_st_e.ptr;
+    a.stats_scratch = ctx->d_stats_scratch.ptr;
+    a.stats_flags = ctx->d_stats_flags.ptr;
+    if (ctx->overlap && ctx->d_extra_scratch.ptr) {
+        a.extra_scratch = ctx->d_extra_scratch.ptr;
+        a.extra_flags = ctx->d_extra_flags.ptr;
         a.aux = ctx->s_aux;
         a.ev_fork = (void*)ctx->ev_fork;
         a.ev_join = (void*)ctx->ev_join;
@@ -888,7 +796,6 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
     return FPL_OK;
 }
 
-/* device staging of one slot for a batch of this size (grown with 25 % headroom; a grow waits for the device) */
 static int ensure_host_streams(fpl_ctx* ctx) {
     if (ctx->stream) return FPL_OK;
     FPL_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -898,137 +805,76 @@ static int ensure_host_streams(fpl_ctx* ctx) {
     return FPL_OK;
 }
 
-static int ensure_host_results(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n_reads) {
-    if (n_reads <= sl.h_res_cap && sl.h_results) return FPL_OK;
-    if (sl.h_results) (void)hipHostFree(sl.h_results);
-    sl.h_results = nullptr;
-    sl.h_res_cap = 0;
-    const u32 cap = n_reads + n_reads / 4 + 1024;
-    FPL_HIP(hipHostMalloc((void**)&sl.h_results, sizeof(fpl_read_result) * (size_t)cap, hipHostMallocDefault));
-    sl.h_res_cap = cap;
-    return FPL_OK;
-}
-/* host_results: false for a text slot -- its device arrays are sized by the most records its bytes COULD hold (one per 64 bytes),
+/* device staging of one slot for a batch of this size, and the page-locked copy of its records.
+   host_results: false for a text slot -- its device arrays are sized by the most records its bytes COULD hold (one per 64 bytes),
    the page-locked host copy of the records by what the chunk turns out to have (text_continue): locking 19 MB of pages per slot
    for the 1 900 records of a 32 MB chunk of long reads was 3 ms of the link standing still, three times at the start of a run */
 static int ensure_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n_reads, uint64_t n_bytes, bool host_results = true) {
-    if (n_bytes > sl.st_bytes || !sl.d_seq) {
-        FPL_HIP(hipDeviceSynchronize());
-        if (sl.d_seq) (void)hipFree(sl.d_seq);
-        if (sl.d_qual) (void)hipFree(sl.d_qual);
-        sl.d_seq = sl.d_qual = nullptr;
-        sl.st_bytes = 0;
-        const uint64_t cap = n_bytes + n_bytes / 4 + 64;
-        FPL_HIP(hipMalloc((void**)&sl.d_seq, cap));
-        FPL_HIP(hipMalloc((void**)&sl.d_qual, cap));
-        sl.st_bytes = cap;
+    if (!sl.d_seq.holds(n_bytes)) {
+        const size_t cap = grown(n_bytes, 64);
+        FPL_HIP(regrow(sl.d_seq.want(cap), sl.d_qual.want(cap)));
     }
-    if (n_reads > sl.st_reads) {
-        FPL_HIP(hipDeviceSynchronize());
-        if (sl.d_off) (void)hipFree(sl.d_off);
-        if (sl.d_results) (void)hipFree(sl.d_results);
-        sl.d_off = nullptr;
-        sl.d_results = nullptr;
-        sl.st_reads = 0;
-        const u32 cap = n_reads + n_reads / 4 + 16;
-        FPL_HIP(hipMalloc((void**)&sl.d_off, sizeof(uint64_t) * ((size_t)cap + 1)));
-        FPL_HIP(hipMalloc((void**)&sl.d_results, sizeof(fpl_read_result) * (size_t)cap));
-        sl.st_reads = cap;
+    if (!sl.d_results.holds(n_reads)) {
+        const size_t cap = grown(n_reads, 16);
+        FPL_HIP(regrow(sl.d_off.want(cap + 1), sl.d_results.want(cap)));
     }
-    if (host_results) return ensure_host_results(ctx, sl, n_reads);
+    if (host_results) FPL_HIP(sl.h_results.grow(n_reads, 1024));
     return FPL_OK;
 }
 
 /* ---- FASTQ text in (ABI v7): csrc/text_parse.h ---- */
 static int ensure_text_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint64_t n_bytes) {
-    const u32 rec_cap = (u32)(n_bytes / 64 + 16);
-    int r = ensure_slot(ctx, sl, rec_cap, n_bytes / 2 + 64, false);
+    fpl_ctx::Slot::Text& t = sl.text;
+    int r = ensure_slot(ctx, sl, (u32)(n_bytes / 64 + 16), n_bytes / 2 + 64, false);
     if (r != FPL_OK) return r;
-    if (!sl.d_hdr) {
-        FPL_HIP(hipMalloc((void**)&sl.d_hdr, sizeof(TextHeader)));
-        FPL_HIP(hipHostMalloc((void**)&sl.h_hdr, sizeof(TextHeader), hipHostMallocDefault));
+    if (!t.d_hdr.ptr) {
+        FPL_HIP(t.d_hdr.alloc(1));
+        FPL_HIP(t.h_hdr.alloc(1));
     }
-    if (n_bytes > sl.text_cap) {
-        FPL_HIP(hipDeviceSynchronize());
-        void* old[] = {sl.d_text, sl.d_nl, sl.d_blk, sl.d_line, sl.d_len};
-        for (void* p : old)
-            if (p) (void)hipFree(p);
-        sl.d_text = nullptr;
-        sl.d_nl = sl.d_blk = sl.d_line = sl.d_len = nullptr;
-        sl.text_cap = 0;
-        sl.rec_cap = 0;
-        const uint64_t cap = n_bytes + n_bytes / 4 + 4096;
-        const u32 rc = (u32)(cap / 64 + 16);
-        FPL_HIP(hipMalloc((void**)&sl.d_text, cap + 16));
-        FPL_HIP(hipMalloc((void**)&sl.d_nl, sizeof(u32) * 4 * (size_t)rc));
-        FPL_HIP(hipMalloc((void**)&sl.d_blk, sizeof(u32) * (size_t)(cap / TP_BLOCK_BYTES + 2)));
-        FPL_HIP(hipMalloc((void**)&sl.d_line, sizeof(u32) * 4 * (size_t)rc));
-        FPL_HIP(hipMalloc((void**)&sl.d_len, sizeof(u32) * (size_t)rc));
-        sl.text_cap = cap;
-        sl.rec_cap = rc;
+    if (!t.d_text.holds(n_bytes + 16)) {
+        const size_t cap = grown(n_bytes, 4096), rc = cap / 64 + 16;
+        FPL_HIP(regrow(t.d_text.want(cap + 16), t.d_nl.want(4 * rc), t.d_blk.want(cap / TP_BLOCK_BYTES + 2), t.d_line.want(4 * rc),
+                       t.d_len.want(rc)));
     }
     return FPL_OK;
 }
 
 /* ---- gzip members of a text batch (ABI v9) and of a BAM batch (ABI v10): csrc/gz_emit.h ---- */
-static int gz_grow(fpl_ctx* ctx, void** p, uint64_t& cap, uint64_t want) { /* bytes; 25 % headroom; a grow waits for the device */
-    if (want <= cap && *p) return FPL_OK;
-    FPL_HIP(hipDeviceSynchronize());
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    const uint64_t c = want + want / 4 + 4096;
-    FPL_HIP(hipMalloc(p, c));
-    cap = c;
-    return FPL_OK;
-}
 /* behind the per-read kernels of the batch, on their stream: where every record's output and every deflate block starts */
 static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
-    if (!sl.d_gz_hdr) {
-        FPL_HIP(hipMalloc((void**)&sl.d_gz_hdr, sizeof(GzHeader)));
-        FPL_HIP(hipHostMalloc((void**)&sl.h_gz_hdr, sizeof(GzHeader), hipHostMallocDefault));
+    fpl_ctx::Slot::Gzip& g = sl.gzip;
+    const bool bam = sl.kind == BatchKind::BAM;
+    if (!g.d_hdr.ptr) {
+        FPL_HIP(g.d_hdr.alloc(1));
+        FPL_HIP(g.h_hdr.alloc(1));
     }
-    const uint64_t blk_want = (sl.bam_gz ? gz_bam_blocks_bound(sl.bam_bases, n) : gz_blocks_bound(sl.text_bytes, n)) + 1;
+    const uint64_t blk_want = (bam ? gz_bam_blocks_bound(sl.bam.bases, n) : gz_blocks_bound(sl.text.bytes, n)) + 1;
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
-    if ((uint64_t)n + 1 > sl.gz_rec_cap || !sl.d_rec_off) {
-        uint64_t cap = 0;
-        sl.gz_rec_cap = 0;
-        const int r = gz_grow(ctx, (void**)&sl.d_rec_off, cap, sizeof(u64) * ((uint64_t)n + 1));
-        if (r != FPL_OK) return r;
-        sl.gz_rec_cap = (u32)std::min<uint64_t>(cap / sizeof(u64), 0xFFFFFFFFull);
+    FPL_HIP(g.d_rec_off.grow((size_t)n + 1, 4096 / sizeof(u64)));
+    if (!g.d_blk_start.holds(blk_want)) {
+        const size_t cap = grown(blk_want, 64, 0xFFFFFFF0u); /* (the kernels take it as 32 bits) */
+        FPL_HIP(regrow(g.d_blk_start.want(cap), g.d_blk_off.want(cap), g.d_blk_size.want(cap), g.d_blk_crc.want(cap)));
     }
-    if (blk_want > sl.gz_blk_cap || !sl.d_gz_blk_start) {
-        FPL_HIP(hipDeviceSynchronize());
-        void* old[] = {sl.d_gz_blk_start, sl.d_gz_blk_off, sl.d_gz_blk_size, sl.d_gz_blk_crc};
-        for (void* p : old)
-            if (p) (void)hipFree(p);
-        sl.d_gz_blk_start = sl.d_gz_blk_off = nullptr;
-        sl.d_gz_blk_size = sl.d_gz_blk_crc = nullptr;
-        sl.gz_blk_cap = 0;
-        const uint64_t cap = std::min<uint64_t>(blk_want + blk_want / 4 + 64, 0xFFFFFFF0ull);
-        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_start, sizeof(uint64_t) * cap));
-        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_off, sizeof(uint64_t) * cap));
-        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_size, sizeof(u32) * cap));
-        FPL_HIP(hipMalloc((void**)&sl.d_gz_blk_crc, sizeof(u32) * cap));
-        sl.gz_blk_cap = (u32)cap;
-    }
+    const u32 blk_cap = (u32)g.d_blk_start.cap;
     hipStream_t st = ctx->stream;
-    if (sl.bam_gz)
-        hipLaunchKernelGGL(k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_bam, (const uint64_t*)sl.d_rec, (const u8*)sl.d_seq,
-                           (const u8*)sl.d_qual, (const uint64_t*)sl.d_off, (const fpl_read_result*)sl.d_results, n, sl.d_rec_off,
-                           sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
+    if (bam)
+        hipLaunchKernelGGL(k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, g.d_rec_off.ptr, g.d_blk_start.ptr, blk_cap - 1, g.d_hdr.ptr);
     else
-        hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line, (const u32*)sl.d_nl,
-                           (const fpl_read_result*)sl.d_results, n, sl.d_rec_off, sl.d_gz_blk_start, sl.gz_blk_cap - 1, sl.d_gz_hdr);
+        hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
+                           (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, g.d_rec_off.ptr, g.d_blk_start.ptr,
+                           blk_cap - 1, g.d_hdr.ptr);
     FPL_HIP(hipGetLastError());
-    FPL_HIP(hipMemcpyAsync(sl.h_gz_hdr, sl.d_gz_hdr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
-    FPL_HIP(hipEventRecord(sl.ev_gz, st));
+    FPL_HIP(hipMemcpyAsync(g.h_hdr.ptr, g.d_hdr.ptr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
+    FPL_HIP(hipEventRecord(g.ev, st));
     return FPL_OK;
 }
 /* the layout is in: buffers of the sizes it found, the other kernels, the member's way back.  *gz / *gz_len: see the header */
 static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t* gz_len) {
-    FPL_HIP(hipEventSynchronize(sl.ev_gz));
-    const GzHeader h = *sl.h_gz_hdr;
+    fpl_ctx::Slot::Gzip& g = sl.gzip;
+    FPL_HIP(hipEventSynchronize(g.ev));
+    const GzHeader h = *g.h_hdr.ptr;
     if (h.status) {
         ctx->err = "gzip layout: more deflate blocks than the bound allows";
         return FPL_ERR_STATE;
@@ -1036,99 +882,101 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     if (h.total == 0) return FPL_OK;
     const u32 n = sl.n_reads;
     const uint64_t out_want = GZ_MEMBER_EXTRA + h.total + (uint64_t)GZ_SLACK * h.n_blocks;
-    int r = gz_grow(ctx, (void**)&sl.d_gz_comp, sl.gz_comp_cap, h.total + 16);
-    if (r != FPL_OK) return r;
-    if (out_want + 16 > sl.gz_out_cap || !sl.d_gz_out) {
-        uint64_t c1 = 0, c2 = 0;
-        if (sl.d_gz_tmp) {
-            FPL_HIP(hipDeviceSynchronize());
-            (void)hipFree(sl.d_gz_tmp);
-            sl.d_gz_tmp = nullptr;
-        }
-        r = gz_grow(ctx, (void**)&sl.d_gz_tmp, c1, out_want + 16);
-        if (r != FPL_OK) return r;
-        r = gz_grow(ctx, (void**)&sl.d_gz_out, c2, out_want + 16);
-        if (r != FPL_OK) return r;
-        sl.gz_out_cap = std::min(c1, c2);
-    }
+    FPL_HIP(g.d_comp.grow(h.total + 16, 4096));
+    FPL_HIP(g.d_tmp.grow(out_want + 16, 4096));
+    FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
-    if (sl.bam_gz)
-        hipLaunchKernelGGL(k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_bam, (const uint64_t*)sl.d_rec,
-                           (const u8*)sl.d_seq, (const u8*)sl.d_qual, (const uint64_t*)sl.d_off, (const fpl_read_result*)sl.d_results, n,
-                           (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
+    if (sl.kind == BatchKind::BAM)
+        hipLaunchKernelGGL(k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+                           (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
     else
-        hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line,
-                           (const u32*)sl.d_nl, (const fpl_read_result*)sl.d_results, n, (const u64*)sl.d_rec_off, sl.d_gz_comp, (u64)h.total);
+        hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
+                           (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr,
+                           g.d_comp.ptr, (u64)h.total);
     const u32 grid = std::max<u32>(1u, std::min<u32>(h.n_blocks, 8u * ctx->n_cu));
-    hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)sl.d_gz_comp, (const u64*)sl.d_gz_blk_start,
-                       (const GzHeader*)sl.d_gz_hdr, sl.d_gz_tmp, sl.d_gz_blk_size, sl.d_gz_blk_crc);
-    hipLaunchKernelGGL(k_gz_finish, dim3(1), dim3(1024), 0, st, (const u32*)sl.d_gz_blk_size, (const u32*)sl.d_gz_blk_crc, (u64*)sl.d_gz_blk_off,
-                       sl.d_gz_hdr, sl.d_gz_out, (u64)out_want);
-    hipLaunchKernelGGL(k_gz_compact, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)sl.d_gz_tmp, (const u64*)sl.d_gz_blk_start,
-                       (const u32*)sl.d_gz_blk_size, (const u64*)sl.d_gz_blk_off, (const GzHeader*)sl.d_gz_hdr, sl.d_gz_out, (u64)out_want);
+    hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_comp.ptr, (const u64*)g.d_blk_start.ptr,
+                       (const GzHeader*)g.d_hdr.ptr, g.d_tmp.ptr, g.d_blk_size.ptr, g.d_blk_crc.ptr);
+    hipLaunchKernelGGL(k_gz_finish, dim3(1), dim3(1024), 0, st, (const u32*)g.d_blk_size.ptr, (const u32*)g.d_blk_crc.ptr,
+                       (u64*)g.d_blk_off.ptr, g.d_hdr.ptr, g.d_out.ptr, (u64)out_want);
+    hipLaunchKernelGGL(k_gz_compact, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_tmp.ptr, (const u64*)g.d_blk_start.ptr,
+                       (const u32*)g.d_blk_size.ptr, (const u64*)g.d_blk_off.ptr, (const GzHeader*)g.d_hdr.ptr, g.d_out.ptr, (u64)out_want);
     FPL_HIP(hipGetLastError());
-    FPL_HIP(hipMemcpyAsync(sl.h_gz_hdr, sl.d_gz_hdr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
-    FPL_HIP(hipEventRecord(sl.ev_gz, st));
-    if (out_want > sl.h_gz_cap) { /* (beside the kernels) */
-        if (sl.h_gz) (void)hipHostFree(sl.h_gz);
-        sl.h_gz = nullptr;
-        sl.h_gz_cap = 0;
-        const uint64_t cap = out_want + out_want / 4 + 4096;
-        FPL_HIP(hipHostMalloc((void**)&sl.h_gz, cap, hipHostMallocDefault));
-        sl.h_gz_cap = cap;
-    }
-    FPL_HIP(hipEventSynchronize(sl.ev_gz));
-    const GzHeader h2 = *sl.h_gz_hdr;
+    FPL_HIP(hipMemcpyAsync(g.h_hdr.ptr, g.d_hdr.ptr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
+    FPL_HIP(hipEventRecord(g.ev, st));
+    FPL_HIP(g.h_out.grow(out_want, 4096)); /* (beside the kernels) */
+    FPL_HIP(hipEventSynchronize(g.ev));
+    const GzHeader h2 = *g.h_hdr.ptr;
     if (h2.status || h2.gz_len == 0 || h2.gz_len > out_want) {
         ctx->err = "gzip member: the kernels report a size outside the bound";
         return FPL_ERR_STATE;
     }
     /* (the kernels are done: the member goes back on the copy stream, beside the next batch's kernels) */
-    FPL_HIP(hipMemcpyAsync(sl.h_gz, sl.d_gz_out, h2.gz_len, hipMemcpyDeviceToHost, ctx->s_d2h));
-    FPL_HIP(hipEventRecord(sl.ev_gz, ctx->s_d2h));
-    FPL_HIP(hipEventSynchronize(sl.ev_gz));
-    *gz = sl.h_gz;
+    FPL_HIP(hipMemcpyAsync(g.h_out.ptr, g.d_out.ptr, h2.gz_len, hipMemcpyDeviceToHost, ctx->s_d2h));
+    FPL_HIP(hipEventRecord(g.ev, ctx->s_d2h));
+    FPL_HIP(hipEventSynchronize(g.ev));
+    *gz = g.h_out.ptr;
     *gz_len = h2.gz_len;
     ctx->gz_batches++;
     return FPL_OK;
+}
+
+/* The second half of every submission, behind whatever brings the reads to the device as CSR arrays (`inputs` says when they
+   are in): the per-read kernels on the compute stream, then the records' way back on a stream of their own, so that they do not
+   queue behind the next batch's input copies.  A BAM batch sends its decoded bases back in front of the records, as soon as the
+   decode is done; a text batch its line starts behind them; a gzip batch has its layout enqueued behind the kernels. */
+static int submit_tail(fpl_ctx* ctx, fpl_ctx::Slot& sl, hipEvent_t inputs, u32 n, uint64_t n_bytes, u32 max_len) {
+    FPL_HIP(hipStreamWaitEvent(ctx->stream, inputs, 0));
+    ctx->next_inputs_event = inputs; /* (the end trims may start as soon as the inputs are in: beside the batch before) */
+    const int rd = fpl_process_batch_device(ctx, sl.d_seq.ptr, sl.d_qual.ptr, sl.d_off.ptr, n, n_bytes, max_len, sl.d_results.ptr, ctx->stream);
+    ctx->next_inputs_event = nullptr;
+    if (rd != FPL_OK) return rd;
+    FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
+    if (sl.kind == BatchKind::BAM) {
+        const fpl_ctx::Slot::Bam& b = sl.bam;
+        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_parsed, 0));
+        if (b.bases && b.seq_out) {
+            FPL_HIP(hipMemcpyAsync(b.seq_out + b.o_begin, sl.d_seq.ptr + b.o_begin, b.bases, hipMemcpyDeviceToHost, ctx->s_d2h));
+            FPL_HIP(hipMemcpyAsync(b.qual_out + b.o_begin, sl.d_qual.ptr + b.o_begin, b.bases, hipMemcpyDeviceToHost, ctx->s_d2h));
+        }
+    }
+    FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_kern, 0));
+    FPL_HIP(hipMemcpyAsync(sl.h_results.ptr, sl.d_results.ptr, sizeof(fpl_read_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (sl.kind == BatchKind::Text)
+        FPL_HIP(hipMemcpyAsync(sl.text.h_line.ptr, sl.text.d_line.ptr, sizeof(u32) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->s_d2h));
+    FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
+    if (sl.gz) return gz_layout(ctx, sl, n); /* (on the compute stream) */
+    return FPL_OK;
+}
+/* after an enqueue error: "nothing is in flight" is what the caller reads into it, and it recycles the host arrays at once.  Copies
+   or kernels that did get enqueued before the failing call may still read them (and the slot): wait them out first. */
+static void drain(fpl_ctx* ctx) {
+    for (hipStream_t st : {ctx->s_h2d, ctx->s_parse, ctx->stream, ctx->s_d2h})
+        if (st) (void)hipStreamSynchronize(st);
+}
+/* the offsets of read i rise and it is no longer than 2^31 - 1; max_len follows the longest read */
+static inline bool read_len_ok(const uint64_t* off, u32 i, u32& max_len) {
+    if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7FFFFFFFull) return false;
+    max_len = std::max(max_len, (u32)(off[i + 1] - off[i]));
+    return true;
 }
 
 /* stage 2 of a text batch: the header is in -- enqueue the per-read kernels and the way back of the records and line starts */
 /* (called by fpl_wait_text only: a submission never waits for a parse, so the next chunk's copy goes out behind this one's at
    once -- no round trip to the host between two chunks on the link -- and a batch that has only been peeked at is in no counter) */
 static int text_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl) {
-    if (sl.kind != 1 || sl.stage != 1) return FPL_OK;
-    sl.stage = 2;
+    if (sl.kind != BatchKind::Text || sl.text.stage != 1) return FPL_OK;
+    sl.text.stage = 2;
     FPL_HIP(hipEventSynchronize(sl.ev_parsed));
-    const TextHeader h = *sl.h_hdr;
+    const TextHeader h = *sl.text.h_hdr.ptr;
     sl.n_reads = 0;
     if (h.status != 0 || h.n_records == 0) return FPL_OK; /* nothing to run: fpl_wait_text reports */
     const u32 n = h.n_records;
-    if (n > sl.h_line_cap) {
-        if (sl.h_line) (void)hipHostFree(sl.h_line);
-        sl.h_line = nullptr;
-        sl.h_line_cap = 0;
-        const u32 cap = n + n / 4 + 16;
-        FPL_HIP(hipHostMalloc((void**)&sl.h_line, sizeof(u32) * 4 * (size_t)cap, hipHostMallocDefault));
-        sl.h_line_cap = cap;
-    }
-    {
-        const int rh = ensure_host_results(ctx, sl, n);
-        if (rh != FPL_OK) return rh;
-    }
-    FPL_HIP(hipStreamWaitEvent(ctx->stream, sl.ev_parsed, 0));
-    ctx->next_inputs_event = sl.ev_parsed; /* (the end trims may start beside the batch before) */
-    const int rd = fpl_process_batch_device(ctx, sl.d_seq, sl.d_qual, sl.d_off, n, h.n_bases, h.max_len, sl.d_results, ctx->stream);
-    ctx->next_inputs_event = nullptr;
-    if (rd != FPL_OK) return rd;
-    FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
-    FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_kern, 0));
-    FPL_HIP(hipMemcpyAsync(sl.h_results, sl.d_results, sizeof(fpl_read_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->s_d2h));
-    FPL_HIP(hipMemcpyAsync(sl.h_line, sl.d_line, sizeof(u32) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->s_d2h));
-    FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
-    sl.n_reads = n;
-    if (sl.gz) return gz_layout(ctx, sl, n);
-    return FPL_OK;
+    if (!sl.text.h_line.holds(4 * (size_t)n)) FPL_HIP(regrow(sl.text.h_line.want(4 * grown(n, 16))));
+    FPL_HIP(sl.h_results.grow(n, 1024));
+    const int r = submit_tail(ctx, sl, sl.ev_parsed, n, h.n_bases, h.max_len);
+    if (r == FPL_OK) sl.n_reads = n;
+    return r;
 }
 int fpl_process_text_async(fpl_ctx* ctx, const uint8_t* text, uint64_t n_bytes) {
     if (!ctx || (n_bytes && !text)) return FPL_ERR_ARG;
@@ -1138,63 +986,65 @@ int fpl_process_text_async(fpl_ctx* ctx, const uint8_t* text, uint64_t n_bytes) 
     if (ctx->hcfg.defer) return FPL_ERR_STATE; /* (--break / --mask read their fragment lists batch by batch: the CSR entry points) */
     int r = FPL_OK;
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
-    sl.kind = 1;
+    fpl_ctx::Slot::Text& t = sl.text;
+    sl.kind = BatchKind::Text;
     sl.gz = ctx->text_gzip;
-    sl.bam_gz = false;
-    sl.stage = 2;
-    sl.cancelled = false;
+    t.stage = 2;
+    t.cancelled = false;
     sl.n_reads = 0;
     sl.rc = FPL_OK;
-    sl.text_bytes = n_bytes;
+    t.bytes = n_bytes;
     r = ensure_host_streams(ctx);
     if (r != FPL_OK) return r;
     r = ensure_text_slot(ctx, sl, n_bytes);
     if (r != FPL_OK) return r;
     if (n_bytes == 0) {
-        memset(sl.h_hdr, 0, sizeof(TextHeader));
-        sl.h_hdr->bad_record = ~0ull;
+        memset(t.h_hdr.ptr, 0, sizeof(TextHeader));
+        t.h_hdr.ptr->bad_record = ~0ull;
         ctx->submitted++;
         return FPL_OK;
     }
     auto enqueue = [&]() -> int {
         /* the upload on the copy stream, the parse on a stream of its own behind it: the NEXT chunk's upload starts the moment this
            one's is done (with the parse on the copy stream the link sat idle for 140 us between two uploads of 590) */
-        FPL_HIP(hipMemcpyAsync(sl.d_text, text, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        u8* const d_text = t.d_text.ptr;
+        u32 *const d_nl = t.d_nl.ptr, *const d_blk = t.d_blk.ptr, *const d_line = t.d_line.ptr, *const d_len = t.d_len.ptr;
+        TextHeader* const d_hdr = t.d_hdr.ptr;
+        FPL_HIP(hipMemcpyAsync(d_text, text, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
         FPL_HIP(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
         hipStream_t st = ctx->s_parse;
         FPL_HIP(hipStreamWaitEvent(st, sl.ev_h2d, 0));
-        FPL_HIP(hipMemsetAsync(sl.d_hdr, 0, sizeof(TextHeader), st));
-        FPL_HIP(hipMemsetAsync(&sl.d_hdr->bad_record, 0xFF, sizeof(u64), st));
+        FPL_HIP(hipMemsetAsync(d_hdr, 0, sizeof(TextHeader), st));
+        FPL_HIP(hipMemsetAsync(&d_hdr->bad_record, 0xFF, sizeof(u64), st));
         const u32 nblk = (u32)((n_bytes + TP_BLOCK_BYTES - 1) / TP_BLOCK_BYTES);
         const u32 rec_cap = (u32)(n_bytes / 64 + 16);
-        hipLaunchKernelGGL(k_text_count, dim3(nblk), dim3(TP_THREADS), 0, st, (const u8*)sl.d_text, (u64)n_bytes, sl.d_blk, sl.d_hdr);
-        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, st, sl.d_blk, nblk, sl.d_hdr);
-        hipLaunchKernelGGL(k_text_fill, dim3(nblk), dim3(TP_THREADS), 0, st, (const u8*)sl.d_text, (u64)n_bytes, (const u32*)sl.d_blk, sl.d_nl,
+        hipLaunchKernelGGL(k_text_count, dim3(nblk), dim3(TP_THREADS), 0, st, (const u8*)d_text, (u64)n_bytes, d_blk, d_hdr);
+        hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(1024), 0, st, d_blk, nblk, d_hdr);
+        hipLaunchKernelGGL(k_text_fill, dim3(nblk), dim3(TP_THREADS), 0, st, (const u8*)d_text, (u64)n_bytes, (const u32*)d_blk, d_nl,
                            4 * rec_cap);
         const u32 rblk = std::min<u32>(std::max<u32>(1u, (rec_cap + 255u) / 256u), 4u * ctx->n_cu);
-        hipLaunchKernelGGL(k_text_records, dim3(rblk), dim3(256), 0, st, (const u8*)sl.d_text, (u64)n_bytes, (const u32*)sl.d_nl, rec_cap,
-                           sl.d_hdr, sl.d_line, sl.d_len);
-        hipLaunchKernelGGL(k_text_offsets, dim3(1), dim3(1024), 0, st, (const u32*)sl.d_len, rec_cap, sl.d_hdr, sl.d_off);
-        hipLaunchKernelGGL(k_text_gather, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.d_text, (const u32*)sl.d_line,
-                           (const u32*)sl.d_len, (const uint64_t*)sl.d_off, (const TextHeader*)sl.d_hdr, rec_cap, sl.d_seq, sl.d_qual);
+        hipLaunchKernelGGL(k_text_records, dim3(rblk), dim3(256), 0, st, (const u8*)d_text, (u64)n_bytes, (const u32*)d_nl, rec_cap,
+                           d_hdr, d_line, d_len);
+        hipLaunchKernelGGL(k_text_offsets, dim3(1), dim3(1024), 0, st, (const u32*)d_len, rec_cap, d_hdr, sl.d_off.ptr);
+        hipLaunchKernelGGL(k_text_gather, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)d_text, (const u32*)d_line,
+                           (const u32*)d_len, (const uint64_t*)sl.d_off.ptr, (const TextHeader*)d_hdr, rec_cap, sl.d_seq.ptr, sl.d_qual.ptr);
         FPL_HIP(hipGetLastError());
-        FPL_HIP(hipMemcpyAsync(sl.h_hdr, sl.d_hdr, sizeof(TextHeader), hipMemcpyDeviceToHost, st));
+        FPL_HIP(hipMemcpyAsync(t.h_hdr.ptr, d_hdr, sizeof(TextHeader), hipMemcpyDeviceToHost, st));
         FPL_HIP(hipEventRecord(sl.ev_parsed, st));
         return FPL_OK;
     };
     r = enqueue();
     if (r != FPL_OK) {
-        if (ctx->s_h2d) (void)hipStreamSynchronize(ctx->s_h2d);
-        if (ctx->s_parse) (void)hipStreamSynchronize(ctx->s_parse);
+        drain(ctx);
         return r;
     }
-    sl.stage = 1;
+    t.stage = 1;
     ctx->submitted++;
     return FPL_OK;
 }
 
 static void text_info(const fpl_ctx::Slot& sl, fpl_text_result* out) {
-    const TextHeader& h = *sl.h_hdr;
+    const TextHeader& h = *sl.text.h_hdr.ptr;
     memset(out, 0, sizeof(*out));
     out->n_lines = h.n_lines;
     out->bad_record = h.bad_record;
@@ -1210,7 +1060,7 @@ static void text_info(const fpl_ctx::Slot& sl, fpl_text_result* out) {
 static fpl_ctx::Slot* text_pending(fpl_ctx* ctx) {
     for (u32 k = ctx->waited; k != ctx->submitted; k++) {
         fpl_ctx::Slot& sl = ctx->slot[k % FPL_MAX_IN_FLIGHT];
-        if (sl.kind == 1 && sl.stage == 1 && !sl.cancelled) return &sl;
+        if (sl.kind == BatchKind::Text && sl.text.stage == 1 && !sl.text.cancelled) return &sl;
     }
     return nullptr;
 }
@@ -1244,7 +1094,7 @@ int fpl_cancel_text(fpl_ctx* ctx) {
     if (!sl) return FPL_ERR_STATE;
     FPL_HIP(hipSetDevice(ctx->device));
     if (sl->rc == FPL_OK) FPL_HIP(hipEventSynchronize(sl->ev_parsed)); /* (its copy and parse read the caller's text) */
-    sl->cancelled = true;
+    sl->text.cancelled = true;
     sl->n_reads = 0;
     return FPL_OK;
 }
@@ -1272,12 +1122,12 @@ static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result**
     if (!ctx || !out) return FPL_ERR_ARG;
     if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
     fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
-    if (sl.kind != 1) return FPL_ERR_STATE; /* (a CSR batch: fpl_wait) */
+    if (sl.kind != BatchKind::Text) return FPL_ERR_STATE; /* (a CSR or BAM batch: fpl_wait) */
     memset(out, 0, sizeof(*out));
     if (results) *results = nullptr;
     if (line_starts) *line_starts = nullptr;
     FPL_HIP(hipSetDevice(ctx->device));
-    if (sl.cancelled) {
+    if (sl.text.cancelled) {
         ctx->waited++;
         out->status = FPL_TEXT_CANCELLED;
         out->bad_record = ~0ull;
@@ -1296,8 +1146,8 @@ static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result**
         if (r != FPL_OK) return r;
     }
     FPL_HIP(hipEventSynchronize(sl.ev_done));
-    if (results) *results = sl.h_results;
-    if (line_starts) *line_starts = sl.h_line;
+    if (results) *results = sl.h_results.ptr;
+    if (line_starts) *line_starts = sl.text.h_line.ptr;
     return FPL_OK;
 }
 
@@ -1308,17 +1158,17 @@ static int wait_batch(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx) return FPL_ERR_ARG;
     if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
     fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
-    if (sl.kind != 0) return FPL_ERR_STATE; /* (a text batch: fpl_wait_text) */
+    if (sl.kind == BatchKind::Text) return FPL_ERR_STATE; /* (fpl_wait_text) */
     ctx->waited++;
     if (sl.rc != FPL_OK) return sl.rc; /* nothing was enqueued behind the failure */
     if (sl.n_reads == 0) return FPL_OK;
     FPL_HIP(hipSetDevice(ctx->device));
-    if (gz && sl.gz && sl.bam_gz) {
+    if (gz && sl.gz) {
         const int r = gz_emit(ctx, sl, gz, gz_len);
         if (r != FPL_OK) return r;
     }
     FPL_HIP(hipEventSynchronize(sl.ev_done));
-    memcpy(sl.user_results, sl.h_results, sizeof(fpl_read_result) * (size_t)sl.n_reads);
+    memcpy(sl.user_results, sl.h_results.ptr, sizeof(fpl_read_result) * (size_t)sl.n_reads);
     return FPL_OK;
 }
 int fpl_wait(fpl_ctx* ctx) { return wait_batch(ctx, nullptr, nullptr); }
@@ -1346,8 +1196,8 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
     /* (a text batch in flight keeps waiting for ITS wait: the kernels of this batch go first -- the order of the kernels is free,
        the slots are collected in the order of submission) */
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
-    sl.kind = 0;
-    sl.gz = sl.bam_gz = false;
+    sl.kind = BatchKind::CSR;
+    sl.gz = false;
     sl.n_reads = n_reads;
     sl.user_results = results;
     sl.rc = FPL_OK;
@@ -1357,11 +1207,8 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
     }
     const uint64_t n_bytes = off[n_reads];
     u32 max_len = 0;
-    for (u32 i = 0; i < n_reads; i++) {
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7FFFFFFFull) return FPL_ERR_ARG;
-        const u32 l = (u32)(off[i + 1] - off[i]);
-        if (l > max_len) max_len = l;
-    }
+    for (u32 i = 0; i < n_reads; i++)
+        if (!read_len_ok(off, i, max_len)) return FPL_ERR_ARG;
     int r = ensure_host_streams(ctx);
     if (r != FPL_OK) return r;
     r = ensure_slot(ctx, sl, n_reads, n_bytes);
@@ -1369,31 +1216,16 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
     /* (the slot's previous batch has been waited for -- FPL_MAX_IN_FLIGHT slots, FIFO -- so its buffers are free) */
     auto enqueue = [&]() -> int {
         if (n_bytes) {
-            FPL_HIP(hipMemcpyAsync(sl.d_seq, seq, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-            FPL_HIP(hipMemcpyAsync(sl.d_qual, qual, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+            FPL_HIP(hipMemcpyAsync(sl.d_seq.ptr, seq, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+            FPL_HIP(hipMemcpyAsync(sl.d_qual.ptr, qual, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
         }
-        FPL_HIP(hipMemcpyAsync(sl.d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(sl.d_off.ptr, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->s_h2d));
         FPL_HIP(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
-        FPL_HIP(hipStreamWaitEvent(ctx->stream, sl.ev_h2d, 0));
-        ctx->next_inputs_event = sl.ev_h2d; /* (the end trims may start as soon as the copies are in: beside the previous batch) */
-        const int rd = fpl_process_batch_device(ctx, sl.d_seq, sl.d_qual, sl.d_off, n_reads, n_bytes, max_len, sl.d_results, ctx->stream);
-        ctx->next_inputs_event = nullptr;
-        if (rd != FPL_OK) return rd;
-        /* the records leave on their own stream, so that they do not queue behind the next batch's input copies */
-        FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
-        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_kern, 0));
-        FPL_HIP(hipMemcpyAsync(sl.h_results, sl.d_results, sizeof(fpl_read_result) * (size_t)n_reads, hipMemcpyDeviceToHost,
-                               ctx->s_d2h));
-        FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
-        return FPL_OK;
+        return submit_tail(ctx, sl, sl.ev_h2d, n_reads, n_bytes, max_len);
     };
     r = enqueue();
     if (r != FPL_OK) {
-        /* "nothing is in flight" is what the caller reads into an error here: it recycles the host arrays at once.  Copies or
-           kernels that did get enqueued before the failing call may still read them (and the slot): wait them out first. */
-        if (ctx->s_h2d) (void)hipStreamSynchronize(ctx->s_h2d);
-        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->s_d2h) (void)hipStreamSynchronize(ctx->s_d2h);
+        drain(ctx);
         return r;
     }
     ctx->submitted++;
@@ -1407,7 +1239,7 @@ int fpl_process_batch_async(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qua
 static int bam_check(const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_start, const uint64_t* off, u32 n_reads, u32* max_len) {
     u32 ml = 0;
     for (u32 i = 0; i < n_reads; i++) {
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7FFFFFFFull) return FPL_ERR_ARG;
+        if (!read_len_ok(off, i, ml)) return FPL_ERR_ARG;
         const uint64_t rs = rec_start[i];
         if (rs > n_bytes || n_bytes - rs < 36) return FPL_ERR_ARG;
         const uint8_t* r = bam + rs;
@@ -1417,7 +1249,6 @@ static int bam_check(const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_s
         if (l_seq > 0x7FFFFFFFu || (uint64_t)l_seq != off[i + 1] - off[i]) return FPL_ERR_ARG;
         const uint64_t need = 36 + l_name + 4 * n_cigar + ((uint64_t)l_seq + 1) / 2 + l_seq;
         if (n_bytes - rs < need) return FPL_ERR_ARG;
-        if (l_seq > ml) ml = l_seq;
     }
     if (max_len) *max_len = ml;
     return FPL_OK;
@@ -1449,8 +1280,8 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         return FPL_ERR_ARG;
     }
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
-    sl.kind = 0; /* (collected by fpl_wait like a CSR batch) */
-    sl.gz = sl.bam_gz = ctx->bam_gzip;
+    sl.kind = BatchKind::BAM;
+    sl.gz = ctx->bam_gzip;
     sl.n_reads = n_reads;
     sl.user_results = results;
     sl.rc = FPL_OK;
@@ -1458,65 +1289,34 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         ctx->submitted++;
         return FPL_OK;
     }
+    fpl_ctx::Slot::Bam& b = sl.bam;
     const uint64_t o_begin = off[0], o_end = off[n_reads];
-    sl.bam_bases = o_end - o_begin;
+    b.o_begin = o_begin;
+    b.bases = o_end - o_begin;
+    b.seq_out = seq_out;
+    b.qual_out = qual_out;
     int r = ensure_host_streams(ctx);
     if (r != FPL_OK) return r;
     r = ensure_slot(ctx, sl, n_reads, o_end + 16); /* (the decode writes whole 16-byte words) */
     if (r != FPL_OK) return r;
-    if (n_bytes + BAM_PAD > sl.bam_cap || !sl.d_bam) {
-        FPL_HIP(hipDeviceSynchronize());
-        if (sl.d_bam) (void)hipFree(sl.d_bam);
-        sl.d_bam = nullptr;
-        sl.bam_cap = 0;
-        const uint64_t cap = n_bytes + n_bytes / 4 + BAM_PAD;
-        FPL_HIP(hipMalloc((void**)&sl.d_bam, cap));
-        sl.bam_cap = cap;
-    }
-    if (n_reads > sl.rec_st_cap || !sl.d_rec) {
-        FPL_HIP(hipDeviceSynchronize());
-        if (sl.d_rec) (void)hipFree(sl.d_rec);
-        sl.d_rec = nullptr;
-        sl.rec_st_cap = 0;
-        const u32 cap = n_reads + n_reads / 4 + 16;
-        FPL_HIP(hipMalloc((void**)&sl.d_rec, sizeof(uint64_t) * (size_t)cap));
-        sl.rec_st_cap = cap;
-    }
+    if (!b.d_bam.holds(n_bytes + BAM_PAD)) FPL_HIP(regrow(b.d_bam.want(grown(n_bytes, BAM_PAD))));
+    FPL_HIP(b.d_rec.grow(n_reads, 16));
     auto enqueue = [&]() -> int {
         /* the upload on the copy stream, the decode on the parse stream behind it (the next batch's upload goes out meanwhile), the
            per-read kernels behind the decode; the records, bases and qualities come back on the way-back stream */
-        FPL_HIP(hipMemcpyAsync(sl.d_bam, bam, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-        FPL_HIP(hipMemcpyAsync(sl.d_rec, rec_start, sizeof(uint64_t) * (size_t)n_reads, hipMemcpyHostToDevice, ctx->s_h2d));
-        FPL_HIP(hipMemcpyAsync(sl.d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(b.d_bam.ptr, bam, n_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(b.d_rec.ptr, rec_start, sizeof(uint64_t) * (size_t)n_reads, hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipMemcpyAsync(sl.d_off.ptr, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->s_h2d));
         FPL_HIP(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
         FPL_HIP(hipStreamWaitEvent(ctx->s_parse, sl.ev_h2d, 0));
-        bam_launch(sl.d_bam, sl.d_rec, sl.d_off, n_reads, o_begin, o_end, sl.d_seq, sl.d_qual, ctx->s_parse);
+        bam_launch(b.d_bam.ptr, b.d_rec.ptr, sl.d_off.ptr, n_reads, o_begin, o_end, sl.d_seq.ptr, sl.d_qual.ptr, ctx->s_parse);
         FPL_HIP(hipGetLastError());
         FPL_HIP(hipEventRecord(sl.ev_parsed, ctx->s_parse));
-        FPL_HIP(hipStreamWaitEvent(ctx->stream, sl.ev_parsed, 0));
-        ctx->next_inputs_event = sl.ev_parsed; /* (the end trims may start as soon as the bases are decoded) */
-        const int rd = fpl_process_batch_device(ctx, sl.d_seq, sl.d_qual, sl.d_off, n_reads, o_end, max_len, sl.d_results, ctx->stream);
-        ctx->next_inputs_event = nullptr;
-        if (rd != FPL_OK) return rd;
-        FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
-        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_parsed, 0));
-        if (o_end > o_begin && seq_out) {
-            FPL_HIP(hipMemcpyAsync(seq_out + o_begin, sl.d_seq + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
-            FPL_HIP(hipMemcpyAsync(qual_out + o_begin, sl.d_qual + o_begin, o_end - o_begin, hipMemcpyDeviceToHost, ctx->s_d2h));
-        }
-        FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_kern, 0));
-        FPL_HIP(hipMemcpyAsync(sl.h_results, sl.d_results, sizeof(fpl_read_result) * (size_t)n_reads, hipMemcpyDeviceToHost,
-                               ctx->s_d2h));
-        FPL_HIP(hipEventRecord(sl.ev_done, ctx->s_d2h));
-        if (sl.gz) return gz_layout(ctx, sl, n_reads); /* (behind the per-read kernels, on their stream) */
-        return FPL_OK;
+        return submit_tail(ctx, sl, sl.ev_parsed, n_reads, o_end, max_len);
     };
     r = enqueue();
     if (r != FPL_OK) {
-        if (ctx->s_h2d) (void)hipStreamSynchronize(ctx->s_h2d);
-        if (ctx->s_parse) (void)hipStreamSynchronize(ctx->s_parse);
-        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->s_d2h) (void)hipStreamSynchronize(ctx->s_d2h);
+        drain(ctx);
         return r;
     }
     ctx->submitted++;
@@ -1532,30 +1332,22 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) return FPL_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return FPL_ERR_HIP;
     const uint64_t o_begin = off[0], o_end = off[n_reads];
-    u8 *d_bam = nullptr, *d_seq = nullptr, *d_qual = nullptr;
-    uint64_t *d_rec = nullptr, *d_off = nullptr;
+    DevBuf<u8> d_bam, d_seq, d_qual;
+    DevBuf<uint64_t> d_rec, d_off;
     const size_t out_bytes = (size_t)((o_end + 15) & ~15ull);
-    int rc = FPL_OK;
-    if (hipMalloc((void**)&d_bam, n_bytes + BAM_PAD) != hipSuccess || hipMalloc((void**)&d_rec, sizeof(uint64_t) * n_reads) != hipSuccess ||
-        hipMalloc((void**)&d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)) != hipSuccess ||
-        hipMalloc((void**)&d_seq, out_bytes + 16) != hipSuccess || hipMalloc((void**)&d_qual, out_bytes + 16) != hipSuccess)
-        rc = FPL_ERR_HIP;
-    if (rc == FPL_OK &&
-        (hipMemcpy(d_bam, bam, n_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(d_rec, rec_start, sizeof(uint64_t) * n_reads, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice) != hipSuccess))
-        rc = FPL_ERR_HIP;
-    if (rc == FPL_OK) {
-        bam_launch(d_bam, d_rec, d_off, n_reads, o_begin, o_end, d_seq, d_qual, 0);
-        if (hipGetLastError() != hipSuccess) rc = FPL_ERR_HIP;
-    }
-    if (rc == FPL_OK && o_end > o_begin &&
-        (hipMemcpy(seq_out + o_begin, d_seq + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess ||
-         hipMemcpy(qual_out + o_begin, d_qual + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = FPL_ERR_HIP;
-    for (void* p : {(void*)d_bam, (void*)d_rec, (void*)d_off, (void*)d_seq, (void*)d_qual})
-        if (p) (void)hipFree(p);
-    return rc;
+    if (d_bam.alloc(n_bytes + BAM_PAD) != hipSuccess || d_rec.alloc(n_reads) != hipSuccess || d_off.alloc((size_t)n_reads + 1) != hipSuccess ||
+        d_seq.alloc(out_bytes + 16) != hipSuccess || d_qual.alloc(out_bytes + 16) != hipSuccess)
+        return FPL_ERR_HIP;
+    if (hipMemcpy(d_bam.ptr, bam, n_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_rec.ptr, rec_start, sizeof(uint64_t) * n_reads, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_off.ptr, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice) != hipSuccess)
+        return FPL_ERR_HIP;
+    bam_launch(d_bam.ptr, d_rec.ptr, d_off.ptr, n_reads, o_begin, o_end, d_seq.ptr, d_qual.ptr, 0);
+    if (hipGetLastError() != hipSuccess) return FPL_ERR_HIP;
+    if (o_end > o_begin && (hipMemcpy(seq_out + o_begin, d_seq.ptr + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess ||
+                            hipMemcpy(qual_out + o_begin, d_qual.ptr + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess))
+        return FPL_ERR_HIP;
+    return FPL_OK;
 }
 
 int fpl_process_batch(fpl_ctx* ctx, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, uint32_t n_reads,
@@ -1684,11 +1476,11 @@ int fpl_get_kernel_times(fpl_ctx* ctx, float* ms, const char** names, int* n, in
 extern "C" int fpl_fragment_counts(fpl_ctx* ctx, uint32_t* n_fragments, uint32_t* n_regions) {
     if (!ctx || !n_fragments || !n_regions) return FPL_ERR_ARG;
     *n_fragments = *n_regions = 0;
-    if (!ctx->hcfg.defer || !ctx->bm.counts) return FPL_OK;
+    if (!ctx->hcfg.defer || !ctx->d_bm_counts.ptr) return FPL_OK;
     FPL_HIP(hipSetDevice(ctx->device));
     FPL_HIP(hipDeviceSynchronize());
     u32 c[4] = {0, 0, 0, 0};
-    FPL_HIP(hipMemcpy(c, ctx->bm.counts, sizeof(c), hipMemcpyDeviceToHost));
+    FPL_HIP(hipMemcpy(c, ctx->d_bm_counts.ptr, sizeof(c), hipMemcpyDeviceToHost));
     if (c[2]) {
         ctx->err = "break/mask lists overflowed their capacity";
         return FPL_ERR_CAPACITY;
@@ -1705,8 +1497,8 @@ extern "C" int fpl_get_fragments(fpl_ctx* ctx, fpl_fragment* fragments, uint32_t
     int r = fpl_fragment_counts(ctx, &nf, &nr);
     if (r != FPL_OK) return r;
     if (n_fragments < nf || n_regions < nr) return FPL_ERR_ARG;
-    if (nf) FPL_HIP(hipMemcpy(fragments, ctx->bm.frags, sizeof(fpl_fragment) * (size_t)nf, hipMemcpyDeviceToHost));
-    if (nr) FPL_HIP(hipMemcpy(regions, ctx->bm.regs, sizeof(fpl_region) * (size_t)nr, hipMemcpyDeviceToHost));
+    if (nf) FPL_HIP(hipMemcpy(fragments, ctx->d_bm_frags.ptr, sizeof(fpl_fragment) * (size_t)nf, hipMemcpyDeviceToHost));
+    if (nr) FPL_HIP(hipMemcpy(regions, ctx->d_bm_regs.ptr, sizeof(fpl_region) * (size_t)nr, hipMemcpyDeviceToHost));
     std::sort(fragments, fragments + nf, [](const fpl_fragment& a, const fpl_fragment& b) {
         return a.read != b.read ? a.read < b.read : a.seq_no < b.seq_no;
     });
@@ -1725,17 +1517,12 @@ extern "C" int fpl_debug_prof(unsigned long long* out, int n) {
 }
 #endif
 
-/* the counting of the detection: tables in device memory (the caller frees what `bufs` lists) */
+/* the counting of the detection: tables in device memory, freed with the caller's KmerTables */
 struct KmerTables {
-    u8* d_seq = nullptr;
-    uint64_t* d_off = nullptr;
-    u32* d_counts = nullptr;
-    unsigned long long *d_pos = nullptr, *d_total = nullptr;
-    void release() {
-        void* ptrs[] = {d_seq, d_off, d_counts, d_pos, d_total};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-    }
+    DevBuf<u8> d_seq;
+    DevBuf<uint64_t> d_off;
+    DevBuf<u32> d_counts;
+    DevBuf<unsigned long long> d_pos, d_total;
 };
 static int count_end_kmers_device(int32_t device, const uint8_t* seq, const uint64_t* off, uint32_t n_reads, int32_t side,
                                   int32_t shift_tail, KmerTables& t) {
@@ -1750,19 +1537,18 @@ static int count_end_kmers_device(int32_t device, const uint8_t* seq, const uint
         if (e != hipSuccess && rc == FPL_OK) rc = FPL_ERR_HIP;
         return e == hipSuccess;
     };
-    if (ok(hipMalloc((void**)&t.d_seq, n_bytes ? n_bytes : 1)) && ok(hipMalloc((void**)&t.d_off, sizeof(uint64_t) * ((size_t)n_reads + 1))) &&
-        ok(hipMalloc((void**)&t.d_counts, sizeof(u32) * n_keys)) && ok(hipMalloc((void**)&t.d_pos, sizeof(unsigned long long) * n_keys)) &&
-        ok(hipMalloc((void**)&t.d_total, sizeof(unsigned long long)))) {
-        ok(hipMemcpy(t.d_seq, seq, n_bytes, hipMemcpyHostToDevice));
-        ok(hipMemcpy(t.d_off, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice));
-        ok(hipMemset(t.d_counts, 0, sizeof(u32) * n_keys));
-        ok(hipMemset(t.d_pos, 0, sizeof(unsigned long long) * n_keys));
-        ok(hipMemset(t.d_total, 0, sizeof(unsigned long long)));
+    if (ok(t.d_seq.alloc(n_bytes ? n_bytes : 1)) && ok(t.d_off.alloc((size_t)n_reads + 1)) && ok(t.d_counts.alloc(n_keys)) &&
+        ok(t.d_pos.alloc(n_keys)) && ok(t.d_total.alloc(1))) {
+        ok(hipMemcpy(t.d_seq.ptr, seq, n_bytes, hipMemcpyHostToDevice));
+        ok(hipMemcpy(t.d_off.ptr, off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice));
+        ok(hipMemset(t.d_counts.ptr, 0, sizeof(u32) * n_keys));
+        ok(hipMemset(t.d_pos.ptr, 0, sizeof(unsigned long long) * n_keys));
+        ok(hipMemset(t.d_total.ptr, 0, sizeof(unsigned long long)));
         if (rc == FPL_OK && n_reads) {
             u32 blocks = (n_reads + 3) / 4;
             if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL(k_count_end_kmers, dim3(blocks), dim3(256), 0, 0, (const u8*)t.d_seq, (const uint64_t*)t.d_off, n_reads,
-                               (int)side, (int)shift_tail, t.d_counts, t.d_pos, t.d_total);
+            hipLaunchKernelGGL(k_count_end_kmers, dim3(blocks), dim3(256), 0, 0, (const u8*)t.d_seq.ptr, (const uint64_t*)t.d_off.ptr, n_reads,
+                               (int)side, (int)shift_tail, t.d_counts.ptr, t.d_pos.ptr, t.d_total.ptr);
             ok(hipGetLastError());
         }
     }
@@ -1776,12 +1562,11 @@ int fpl_count_end_kmers(int32_t device, const uint8_t* seq, const uint64_t* off,
     int rc = count_end_kmers_device(device, seq, off, n_reads, side, shift_tail, t);
     if (rc == FPL_OK) {
         const size_t n_keys = (size_t)pick::NKEYS;
-        if (hipMemcpy(counts, t.d_counts, sizeof(u32) * n_keys, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(position_acc, t.d_pos, sizeof(unsigned long long) * n_keys, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(total, t.d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(counts, t.d_counts.ptr, sizeof(u32) * n_keys, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(position_acc, t.d_pos.ptr, sizeof(unsigned long long) * n_keys, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(total, t.d_total.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
             rc = FPL_ERR_HIP;
     }
-    t.release();
     return rc;
 }
 
@@ -1791,16 +1576,16 @@ int fpl_pick_adapter(int32_t device, const uint8_t* seq, const uint64_t* off, ui
                      int32_t is_rna, fpl_adapter_pick* out) {
     if (!out) return FPL_ERR_ARG;
     KmerTables t;
-    pick::Pick* d_pick = nullptr;
+    DevBuf<pick::Pick> d_pick;
     int rc = count_end_kmers_device(device, seq, off, n_reads, side, shift_tail, t);
-    if (rc == FPL_OK && hipMalloc((void**)&d_pick, sizeof(pick::Pick)) != hipSuccess) rc = FPL_ERR_HIP;
+    if (rc == FPL_OK && d_pick.alloc(1) != hipSuccess) rc = FPL_ERR_HIP;
     if (rc == FPL_OK) {
-        hipLaunchKernelGGL(k_pick_adapter, dim3(1), dim3(1024), 0, 0, (const u32*)t.d_counts, (const unsigned long long*)t.d_pos,
-                           (int)(is_rna != 0), d_pick);
+        hipLaunchKernelGGL(k_pick_adapter, dim3(1), dim3(1024), 0, 0, (const u32*)t.d_counts.ptr,
+                           (const unsigned long long*)t.d_pos.ptr, (int)(is_rna != 0), d_pick.ptr);
         pick::Pick p;
         unsigned long long total = 0;
-        if (hipGetLastError() != hipSuccess || hipMemcpy(&p, d_pick, sizeof(p), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(&total, t.d_total, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipGetLastError() != hipSuccess || hipMemcpy(&p, d_pick.ptr, sizeof(p), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(&total, t.d_total.ptr, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess)
             rc = FPL_ERR_HIP;
         else {
             memset(out, 0, sizeof(*out));
@@ -1812,8 +1597,6 @@ int fpl_pick_adapter(int32_t device, const uint8_t* seq, const uint64_t* off, ui
             memcpy(out->seq, p.seq, sizeof(p.seq));
         }
     }
-    if (d_pick) (void)hipFree(d_pick);
-    t.release();
     return rc;
 }
 
