@@ -65,9 +65,7 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 __device__ __forceinline__ u32 shfl_u32(u32 v, int src) { return (u32)__shfl((int)v, src, 64); }
-__device__ __forceinline__ int shfl_i32(int v, int src) { return __shfl(v, src, 64); }
 __device__ __forceinline__ u32 shfl_up_u32(u32 v, unsigned d) { return (u32)__shfl_up((int)v, d, 64); }
-__device__ __forceinline__ u32 shfl_down_u32(u32 v, unsigned d) { return (u32)__shfl_down((int)v, d, 64); }
 __device__ __forceinline__ u32 shfl_xor_u32(u32 v, int m) { return (u32)__shfl_xor((int)v, m, 64); }
 __device__ __forceinline__ u64 shfl_u64(u64 v, int src) {
     u32 lo = shfl_u32((u32)v, src), hi = shfl_u32((u32)(v >> 32), src);
@@ -131,15 +129,6 @@ __device__ __forceinline__ u32 op_add_u32(u32 a, u32 b) { return a + b; }
 __device__ __forceinline__ u32 op_max_u32(u32 a, u32 b) { return a > b ? a : b; }
 __device__ __forceinline__ u32 op_min_u32(u32 a, u32 b) { return a < b ? a : b; }
 #endif
-/* the value of the next lane (lane 63 gets 0): DPP wave_shl:1, no LDS */
-__device__ __forceinline__ u32 wave_next_u32(u32 v) {
-#ifdef FPL_EMU
-    const u32 o = shfl_down_u32(v, 1);
-    return lane_id() == 63 ? 0u : o;
-#else
-    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false);
-#endif
-}
 /* the value of the previous lane (lane 0 gets `first`): DPP wave_shr:1, no LDS */
 __device__ __forceinline__ u32 wave_prev_u32(u32 v, u32 first) {
 #ifdef FPL_EMU
@@ -375,16 +364,6 @@ __device__ __forceinline__ u32 popc_acc(u32 x, u32 acc) {
 #else
     u32 r;
     asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-#endif
-}
-/* (a & b) | c in one VALU op (v_and_or_b32; b wave-uniform) */
-__device__ __forceinline__ u32 and_or(u32 a, u32 b, u32 c) {
-#ifdef FPL_EMU
-    return (a & b) | c;
-#else
-    u32 r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
     return r;
 #endif
 }

@@ -32,14 +32,15 @@ struct DevAdapter {
        adapter: the window Hamming scans of k_trim_ends count matches as popcount(text nibbles & these) */
     uint32_t onehot[8];
     /* the Peq words of the letters A, C, T, G (code = (ASCII >> 1) & 3) in one place, for the lane-per-adapter filter of
-       the FASTA chain (k_trim_ends, fasta_may_trim): the whole adapter (first 64 columns), its last 16 bases (start
-       trim's partial pattern) and its first 16 (end trim's) */
+       the FASTA chain (k_trim_ends, fasta_may_trim32).  The whole adapter (first 64 columns), its last 16 bases and its
+       first 16: copied into the filter's table but read by no search (they served a two-run form of the filter that is no
+       longer in the tree, docs/kernels.md; the fields keep their place so that the layout stays) */
     uint64_t peq4_full[4];
     uint32_t peq4_s16[4];
     uint32_t peq4_e16[4];
-    /* ... and for its cheaper form (FPL_OPT_FASTAFILTER 2): the first min(32, len) bases in reading order (end trim) and the
-       last min(32, len) bases in REVERSE order (start trim, whose window is then walked backwards): in both the trim's
-       16-base partial pattern is the first 16 columns */
+    /* What the filter searches for: the first min(32, len) bases in reading order (end trim) and the last min(32, len)
+       bases in REVERSE order (start trim, whose window is then walked backwards): in both the trim's 16-base partial
+       pattern is the first 16 columns */
     uint32_t peq4_e32[4];
     uint32_t peq4_s32r[4];
 };

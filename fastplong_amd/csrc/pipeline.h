@@ -258,8 +258,7 @@ inline size_t stats_scratch_slabs(u32 n_reads, uint64_t n_bytes, u32 max_read_le
     const u32 n_tiles = cdiv(max_read_len ? max_read_len : 1, FS_T);
     const u32 mean_len = n_reads ? (u32)(n_bytes / n_reads) : 0;
     const u32 per = stats_items_per_slice(n_reads, mean_len, n_cu, tune);
-    u32 slices = cdiv(n_reads ? n_reads : 1, per);
-    if (FPL_OPT_SORTSTATS) slices = stats_sorted_max_slices(n_reads, per, tune);
+    u32 slices = stats_sorted_max_slices(n_reads, per, tune);
     if (slices < FS_EXTRA_BLOCKS) slices = FS_EXTRA_BLOCKS;
     return (size_t)slices * n_tiles;
 }
@@ -268,20 +267,17 @@ inline size_t stats_scratch_slabs(u32 n_reads, uint64_t n_bytes, u32 max_read_le
  * beyond that -- hundreds of millions of reads next to a read of hundreds of megabases -- takes the plain walk; with --break /
  * --mask no read is counted post-filter by the sorted pass: the plain walk does) */
 inline bool stats_takes_sorted(u32 n_reads, uint64_t n_bytes, u32 max_read_len, u32 n_cu, const StatsTune& tune, bool defer) {
-    if (!FPL_OPT_SORTSTATS || defer || n_reads == 0 || !stats_use_sorted(n_reads, tune)) return false;
+    if (defer || n_reads == 0 || !stats_use_sorted(n_reads, tune)) return false;
     const u32 n_tiles = cdiv(max_read_len ? max_read_len : 1, FS_T);
     const u32 per = stats_items_per_slice(n_reads, (u32)(n_bytes / n_reads), n_cu, tune);
     return (uint64_t)stats_sorted_max_slices(n_reads, per, tune) * n_tiles < 0xFFFFFFF0ull;
 }
 
-#ifndef FPL_OPT_BATCH
-#define FPL_OPT_BATCH 1 /* the usual adapter set goes through k_trim_ends_batched (confirmations 64 reads at a time) */
-#endif
 /* do the end trims of a batch run in k_trim_ends_batched (the usual adapter set, 64 reads per wave)? */
 constexpr u32 TRIM_BATCH_MIN_READS = FPL_FORM_TRIM_BATCHED_MIN;
 inline bool trim_takes_batched(u32 n_reads, int trim_mode, const StatsTune& tune) {
     const u32 batch_min = tune.trim_batch_min ? tune.trim_batch_min : TRIM_BATCH_MIN_READS;
-    return (trim_mode == 1 || trim_mode == 2) && FPL_OPT_BATCH && n_reads >= batch_min;
+    return (trim_mode == 1 || trim_mode == 2) && n_reads >= batch_min;
 }
 /* is a batch large enough for its end trims to be worth a stream of their own (two more event hand-overs per batch)? */
 inline bool trim_worth_ahead(u32 n_reads, const StatsTune& tune) {
@@ -340,7 +336,7 @@ inline void enqueue_batch(const BatchArgs& a, fpl_stream_t stream, Mark&& mark) 
                    read from the state the first kernel left (c5: 4.3 of the chain kernel's 15 ms were those four steps) */
                 FPL_LAUNCH((k_trim_ends_batched<KWAVES, 8, true>), dim3(gblocks), block, ts, a.seq, a.qual, a.off, n, a.n_bytes, a.cfg,
                            a.ads, a.state, a.counters, a.C, a.work_ctr + 2);
-                if (FPL_OPT_ONEFP && a.n_fasta <= 64) /* one group of adapters: one Peq table per block */
+                if (a.n_fasta <= 64) /* one group of adapters: one Peq table per block */
                     FPL_LAUNCH((k_trim_ends<KWAVES, 2, true>), dim3(blocks), block, ts, a.seq, a.qual, a.off, n, a.n_bytes, a.cfg,
                                a.ads, a.state, a.counters, a.C, 1);
                 else

@@ -217,7 +217,7 @@ def test_fasta_filter_packed_scores_bit_exact(orc, engine_mod, lens, ed_max, n_a
                                             int(os.environ.get("FPL_FUZZ_FASTA_FROM", "0")) + int(os.environ.get("FPL_FUZZ_FASTA", "8")))))
 def test_random_fasta_sets_of_16_to_64_mers_bit_exact(orc, engine_mod, seed):
     """adapter sets made of 16..64-base ACGT adapters only (k_trim_ends<2>: the lane-per-adapter filter in front of the exact
-    trims, fasta_may_trim) -- 1, 3, 64, 65 and 130 FASTA adapters (one, two and three groups of 64 lanes), mutated /
+    trims, fasta_may_trim32) -- 1, 3, 64, 65 and 130 FASTA adapters (one, two and three groups of 64 lanes), mutated /
     truncated copies near both ends, every ed_max; FPL_FUZZ_FASTA=<n> widens it for a soak"""
     rng = np.random.default_rng(52000 + seed)
     rnd = lambda n: "".join("ACGT"[i] for i in rng.integers(0, 4, int(n)))  # noqa: E731

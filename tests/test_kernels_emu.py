@@ -230,7 +230,7 @@ def test_emulated_sorted_statistics_pass_row_setup(orc, monkeypatch, opts):
 
 
 def _reads_for_kmer6(seed, n=100):
-    """reads for the 6-mer table of k_stats_sorted (FPL_OPT_KMER6): N's at every offset of a lane's eight bytes (a window pair
+    """reads for the 6-mer table of k_stats_sorted: N's at every offset of a lane's eight bytes (a window pair
     that loses its first or its second window takes the 5-mer table), runs of N, bytes of the base classes 0 and 2 (low three
     bits 000 / 010: '@' 'H' 'X' 'p' '*' 'B' 'R' 'j' -- counted with global atomics, their rows walked byte by byte) in rows
     inside r1, across both ends of r1 (adapters at both ends, low-quality tails for the quality cut) and in reads that fail

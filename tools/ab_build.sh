@@ -1,6 +1,8 @@
 #!/bin/bash
 # measurement aid: build kernel variants of libfastplong_amd.so side by side (gpurun_out/ab/<name>.so)
-#   tools/ab_build.sh name "-DFPL_OPT_HIST=0 ..." [source-dir]
+#   tools/ab_build.sh name "-DFPL_REDO_WAVES=4 ..." [source-dir]
+# (the flags set numeric tunables.  An A/B of two implementations starts as a switch local to the working tree; when it is
+#  decided, the losing side is deleted, not kept behind the switch)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; FLAGS=$2; SRC=${3:-$ROOT/fastplong_amd/csrc}
