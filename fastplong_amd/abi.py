@@ -155,6 +155,14 @@ FRAGMENT_DTYPE = [
 ]
 REGION_DTYPE = [("start", "<u4"), ("len", "<u4")]
 
+# struct fpl_bgzf_block (32 bytes): one BGZF block of fpl_inflate_bgzf; status: FPL_BGZF_*
+BGZF_BLOCK_DTYPE = [("comp_off", "<u8"), ("out_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("status", "<u4")]
+FPL_BGZF_OK = 0
+FPL_BGZF_MALFORMED = 1
+FPL_BGZF_SIZE = 2
+FPL_BGZF_CRC = 3
+FPL_BGZF_OVERRUN = 4
+
 # ---- flat int64 counter layout (see the header) -------------------------------------------
 FPL_CYC_STRIDE = 32
 FPL_STATS_TAIL = 128 * 3 + 1024 + 2

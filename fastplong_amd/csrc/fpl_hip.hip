@@ -23,6 +23,7 @@
 #include "text_parse.h"
 #include "gz_emit.h"
 #include "bam_decode.h"
+#include "bgzf_inflate.h"
 
 using namespace fpl;
 
@@ -162,6 +163,15 @@ struct fpl_ctx {
             ctx->err = std::string(#call) + ": " + hipGetErrorString(e__);                    \
             return FPL_ERR_HIP;                                                               \
         }                                                                                     \
+    } while (0)
+
+/* the same for the inflater's call (no context to keep the text in): what is in flight is waited for before the call returns */
+#define FPL_HIP_RC(call)                                  \
+    do {                                                  \
+        if ((call) != hipSuccess) {                       \
+            (void)hipStreamSynchronize(inf->stream);      \
+            return FPL_ERR_HIP;                           \
+        }                                                 \
     } while (0)
 
 extern "C" {
@@ -1347,6 +1357,87 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
     if (o_end > o_begin && (hipMemcpy(seq_out + o_begin, d_seq.ptr + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess ||
                             hipMemcpy(qual_out + o_begin, d_qual.ptr + o_begin, o_end - o_begin, hipMemcpyDeviceToHost) != hipSuccess))
         return FPL_ERR_HIP;
+    return FPL_OK;
+}
+
+/* ---- BGZF inflate (bgzf_inflate.h): a handle of its own, no context ---- */
+struct fpl_inflater {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    DevBuf<u8> d_comp, d_out;
+    DevBuf<fpl_bgzf_block> d_blocks;
+    DevBuf<u32> d_next; /* the kernel's work counter */
+    int n_cu = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> runs; /* output ranges to bring back, merged */
+};
+
+fpl_inflater* fpl_inflater_create(int32_t device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return nullptr;
+    if (hipSetDevice(device) != hipSuccess) return nullptr;
+    fpl_inflater* inf = new (std::nothrow) fpl_inflater();
+    if (!inf) return nullptr;
+    inf->device = device;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || hipStreamCreateWithFlags(&inf->stream, hipStreamNonBlocking) != hipSuccess ||
+        inf->d_next.alloc(1) != hipSuccess) {
+        fpl_inflater_destroy(inf);
+        return nullptr;
+    }
+    inf->n_cu = prop.multiProcessorCount;
+    return inf;
+}
+
+void fpl_inflater_destroy(fpl_inflater* inf) {
+    if (!inf) return;
+    if (inf->device >= 0) (void)hipSetDevice(inf->device);
+    if (inf->stream) {
+        (void)hipStreamSynchronize(inf->stream);
+        (void)hipStreamDestroy(inf->stream);
+    }
+    delete inf;
+}
+
+int fpl_inflate_bgzf(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes, fpl_bgzf_block* blocks, uint32_t n_blocks, uint8_t* out,
+                     uint64_t out_bytes) {
+    if (!inf) return FPL_ERR_ARG;
+    if (n_blocks == 0) return FPL_OK;
+    if (!blocks || (comp_bytes && !comp) || (out_bytes && !out)) return FPL_ERR_ARG;
+    inf->runs.clear();
+    for (uint32_t i = 0; i < n_blocks; i++) { /* every range, before anything is enqueued */
+        const fpl_bgzf_block& d = blocks[i];
+        if (d.comp_len > BGZF_MAX_COMP || d.isize > BGZF_MAX_ISIZE || d.comp_off > comp_bytes || comp_bytes - d.comp_off < d.comp_len ||
+            d.out_off > out_bytes || out_bytes - d.out_off < d.isize)
+            return FPL_ERR_ARG;
+        if (d.isize) inf->runs.emplace_back(d.out_off, d.out_off + d.isize);
+    }
+    std::sort(inf->runs.begin(), inf->runs.end());
+    size_t n_runs = 0;
+    for (const auto& r : inf->runs) { /* ranges that touch are one copy: a reader's window comes back in one */
+        if (n_runs && r.first <= inf->runs[n_runs - 1].second)
+            inf->runs[n_runs - 1].second = std::max(inf->runs[n_runs - 1].second, r.second);
+        else
+            inf->runs[n_runs++] = r;
+    }
+    FPL_HIP_RC(hipSetDevice(inf->device));
+    FPL_HIP_RC(inf->d_comp.grow((size_t)comp_bytes + 1, 4096));
+    FPL_HIP_RC(inf->d_out.grow((size_t)out_bytes + 1, 4096));
+    FPL_HIP_RC(inf->d_blocks.grow(n_blocks, 64));
+    hipStream_t s = inf->stream;
+    if (comp_bytes) FPL_HIP_RC(hipMemcpyAsync(inf->d_comp.ptr, comp, comp_bytes, hipMemcpyHostToDevice, s));
+    FPL_HIP_RC(hipMemcpyAsync(inf->d_blocks.ptr, blocks, sizeof(fpl_bgzf_block) * (size_t)n_blocks, hipMemcpyHostToDevice, s));
+    FPL_HIP_RC(hipMemsetAsync(inf->d_next.ptr, 0, sizeof(u32), s));
+    /* a wave per block; as many workgroups as the device keeps resident (the tables' LDS bounds them), the rest off the counter */
+    const u32 per_cu = std::max<u32>(1, std::min<u32>(8, (u32)(160u * 1024 / (sizeof(BgzfWaveLds) * (BGZF_THREADS / WAVE) + 1024))));
+    const u32 grid = std::min<u32>((n_blocks + BGZF_THREADS / WAVE - 1) / (BGZF_THREADS / WAVE), (u32)inf->n_cu * per_cu);
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3(grid), dim3(BGZF_THREADS), 0, s, (const u8*)inf->d_comp.ptr, inf->d_blocks.ptr, n_blocks, inf->d_out.ptr,
+                       inf->d_next.ptr);
+    FPL_HIP_RC(hipGetLastError());
+    for (size_t k = 0; k < n_runs; k++)
+        FPL_HIP_RC(hipMemcpyAsync(out + inf->runs[k].first, inf->d_out.ptr + inf->runs[k].first, inf->runs[k].second - inf->runs[k].first,
+                                  hipMemcpyDeviceToHost, s));
+    FPL_HIP_RC(hipMemcpyAsync(blocks, inf->d_blocks.ptr, sizeof(fpl_bgzf_block) * (size_t)n_blocks, hipMemcpyDeviceToHost, s));
+    FPL_HIP_RC(hipStreamSynchronize(s));
     return FPL_OK;
 }
 

@@ -26,6 +26,7 @@ EXPORTS = [
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
+    "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy",
 ]
 
 
@@ -150,6 +151,13 @@ def load_library(path=None):
         L.fpl_set_bam_gzip.argtypes = [C.c_void_p, C.c_int]
         L.fpl_wait_bam_gz.restype = C.c_int
         L.fpl_wait_bam_gz.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
+        L.fpl_inflater_create.restype = C.c_void_p
+        L.fpl_inflater_create.argtypes = [C.c_int32]
+        L.fpl_inflate_bgzf.restype = C.c_int
+        L.fpl_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
+        L.fpl_inflater_destroy.restype = None
+        L.fpl_inflater_destroy.argtypes = [C.c_void_p]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -172,6 +180,46 @@ def decode_bam(device, bam, rec_start, off):
     if rc != abi.FPL_OK:
         raise FplError("fpl_decode_bam: %s" % L.fpl_strerror(rc).decode())
     return seq[:total], qual[:total]
+
+
+class Inflater:
+    """One fpl_inflater: BGZF blocks inflated on a device, without a context (fpl_inflate_bgzf)."""
+
+    def __init__(self, device=0, lib=None):
+        self.L = lib if lib is not None else load_library()
+        if not hasattr(self.L, "fpl_inflate_bgzf"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_inflate_bgzf")
+        self.h = self.L.fpl_inflater_create(int(device))
+        if not self.h:
+            raise FplError("fpl_inflater_create: %s" % self.L.fpl_strerror(abi.FPL_ERR_NO_DEVICE).decode())
+
+    def inflate(self, comp, blocks, out=None):
+        """comp: the payloads (uint8); blocks: an array of abi.BGZF_BLOCK_DTYPE (comp_off, out_off, comp_len, isize, crc32).
+        out: the buffer the blocks' ranges are written into (bytes outside them are left alone); made here, zeroed and as long
+        as the furthest range, when not given.  -> (out, status): status[i] 0 = block i inflated, size and CRC-32 agree."""
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        blk = np.array(blocks, dtype=np.dtype(abi.BGZF_BLOCK_DTYPE), copy=True, ndmin=1)
+        if out is None:
+            end = int((blk["out_off"] + blk["isize"]).max()) if len(blk) else 0
+            out = np.zeros(end, np.uint8)
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("out must be a writable contiguous uint8 array")
+        rc = self.L.fpl_inflate_bgzf(self.h, comp.ctypes.data if len(comp) else None, len(comp), blk.ctypes.data if len(blk) else None,
+                                     len(blk), out.ctypes.data if len(out) else None, len(out))
+        if rc != abi.FPL_OK:
+            raise FplError("fpl_inflate_bgzf: %s" % self.L.fpl_strerror(rc).decode())
+        return out, blk["status"].copy()
+
+    def close(self):
+        if self.h:
+            self.L.fpl_inflater_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _b(s):

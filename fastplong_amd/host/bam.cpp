@@ -39,6 +39,19 @@ uint32_t bgzf_block_len(const uint8_t* p, size_t n) {
     return 0;
 }
 
+/* where the deflate payload of the block starts: behind the member's header -- 10 bytes, the extra field, and, which BGZF does not
+   allow but some writers set, a name, a comment, a header CRC (libdeflate skips them too); 0: the header runs into the trailer */
+uint32_t bgzf_payload_offset(const uint8_t* blk, uint32_t len) {
+    uint32_t hdr = 12 + rd16(blk + 10);
+    for (const uint8_t f : {(uint8_t)8, (uint8_t)16})
+        if (blk[3] & f) {
+            while (hdr < len - 8 && blk[hdr]) hdr++;
+            hdr++;
+        }
+    if (blk[3] & 2) hdr += 2;
+    return hdr > len - 8 ? 0 : hdr;
+}
+
 /* one BGZF block -> exactly isize bytes at out, its CRC checked (libdeflate checks the trailer itself; zlib: raw inflate + crc32) */
 bool inflate_block(const uint8_t* blk, uint32_t len, uint32_t isize, uint8_t* out) {
     size_t used = 0, made = 0;
@@ -56,16 +69,8 @@ bool inflate_block(const uint8_t* blk, uint32_t len, uint32_t isize, uint8_t* ou
     } else {
         inflateReset(zs);
     }
-    /* the member's header: 10 bytes, the extra field, and -- which BGZF does not allow but some writers set -- a name, a comment, a
-       header CRC (libdeflate skips them too) */
-    uint32_t hdr = 12 + rd16(blk + 10);
-    for (const uint8_t f : {(uint8_t)8, (uint8_t)16})
-        if (blk[3] & f) {
-            while (hdr < len - 8 && blk[hdr]) hdr++;
-            hdr++;
-        }
-    if (blk[3] & 2) hdr += 2;
-    if (hdr > len - 8) return false;
+    const uint32_t hdr = bgzf_payload_offset(blk, len);
+    if (!hdr) return false;
     zs->next_in = (Bytef*)(blk + hdr);
     zs->avail_in = len - hdr - 8;
     uint8_t dummy = 0;
@@ -110,6 +115,30 @@ BamReader::~BamReader() {
 }
 
 bool BamReader::read_comp(uint64_t off, uint64_t len) {
+    if (inflate_fn_) { /* the same rule over the page-locked buffer: pread puts the file's bytes where the upload reads them */
+        const uint64_t size = pin_comp_.size();
+        if (off >= comp_off_ && off + len <= comp_off_ + size) return true;
+        uint64_t have = 0;
+        if (off >= comp_off_ && off < comp_off_ + size) {
+            have = comp_off_ + size - off;
+            memmove(pin_comp_.data(), pin_comp_.data() + (off - comp_off_), (size_t)have);
+        }
+        const uint64_t want = min<uint64_t>(max<uint64_t>(2 * len, 4u << 20), file_size_ - off);
+        if (want < len) return false;
+        pin_comp_.resize_uninit((size_t)have); /* (a grow copies what the buffer holds) */
+        pin_comp_.resize_uninit((size_t)want);
+        comp_off_ = off;
+        uint64_t got = have;
+        while (got < want) {
+            const ssize_t r = pread(fd_, pin_comp_.data() + got, (size_t)(want - got), (off_t)(off + got));
+            if (r <= 0) {
+                pin_comp_.resize_uninit((size_t)got);
+                return false;
+            }
+            got += (uint64_t)r;
+        }
+        return true;
+    }
     if (off >= comp_off_ && off + len <= comp_off_ + comp_.size()) return true;
     /* keep [off, end of what is there), read the rest behind it: at least twice what the window asked for (fewer, larger reads) */
     vector<uint8_t> keep;
@@ -141,7 +170,7 @@ bool BamReader::next_blocks(uint64_t want, vector<Block>& out) {
             err_ = "reading the BAM input failed: " + path_;
             return false;
         }
-        const uint8_t* p = comp_.data() + (pos - comp_off_);
+        const uint8_t* p = comp_data() + (pos - comp_off_);
         const uint32_t len = bgzf_block_len(p, (size_t)head);
         if (!len) {
             err_ = "BAM input: no BGZF block at file offset " + to_string(pos) + " (damaged or not a BAM file)";
@@ -155,7 +184,7 @@ bool BamReader::next_blocks(uint64_t want, vector<Block>& out) {
             err_ = "reading the BAM input failed: " + path_;
             return false;
         }
-        p = comp_.data() + (pos - comp_off_);
+        p = comp_data() + (pos - comp_off_);
         const uint32_t isize = rd32(p + len - 4);
         if (isize > 65536) {
             err_ = "BAM input: the BGZF block at file offset " + to_string(pos) + " has a bad size";
@@ -287,6 +316,9 @@ uint32_t BamReader::fill(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint6
         const uint64_t size = b.bam.size();
         /* the next window: what the batch still takes (a window at most), and at least what the record in hand needs */
         uint64_t want = min<uint64_t>(window_, max_bytes > size ? max_bytes - size : 1);
+        /* with an inflater: everything the batch still takes, so that one call carries as many blocks as the batch allows (a
+           caller without a byte bound keeps the window) */
+        if (inflate_fn_ && max_bytes < (1ull << 40)) want = max_bytes > size ? max_bytes - size : 1;
         if (need_ > size - wpos_) want = max<uint64_t>(want, need_ - (size - wpos_));
         if (!next_blocks(want, blocks)) return 0;
         if (blocks.empty()) { /* end of the file */
@@ -308,12 +340,45 @@ uint32_t BamReader::fill(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint6
         b.bam.reserve(size + add);
         b.bam.resize_uninit(size + add);
         uint8_t* dst = b.bam.data();
-        const uint8_t* src = comp_.data();
+        const uint8_t* src = comp_data();
         const uint64_t src_off = comp_off_;
+        /* the blocks the host inflates: all of them, or with an inflater those it did not vouch for (and the empty ones, which
+           need no device but keep the host's check of their bytes) */
+        vector<uint32_t> todo;
+        bool all = true;
+        if (inflate_fn_) {
+            const uint64_t w0 = blocks.front().file_off, w1 = blocks.back().file_off + blocks.back().len;
+            dev_desc_.clear();
+            vector<uint32_t> which;
+            for (size_t i = 0; i < blocks.size(); i++) {
+                const Block& k = blocks[i];
+                const uint32_t hdr = k.isize ? bgzf_payload_offset(src + (k.file_off - src_off), k.len) : 0;
+                if (!hdr) {
+                    todo.push_back((uint32_t)i);
+                    continue;
+                }
+                const uint8_t* blk = src + (k.file_off - src_off);
+                dev_desc_.push_back(fpl_bgzf_block{k.file_off - w0 + hdr, at[i] - size, k.len - hdr - 8, k.isize, rd32(blk + k.len - 8), 1u});
+                which.push_back((uint32_t)i);
+            }
+            const bool ran = dev_desc_.empty() || inflate_fn_(inflate_user_, src + (w0 - src_off), w1 - w0, dev_desc_.data(), (uint32_t)dev_desc_.size(),
+                                                              dst + size, add) == 0;
+            for (size_t k = 0; k < which.size(); k++) {
+                if (ran && dev_desc_[k].status == 0) {
+                    dev_blocks_++;
+                } else {
+                    todo.push_back(which[k]);
+                    if (ran) refused_blocks_++;
+                }
+            }
+            all = false;
+        }
+        const size_t n_todo = all ? blocks.size() : todo.size();
         std::atomic<int64_t> bad{-1};
-        const int T = (int)min<size_t>(blocks.size(), (size_t)threads);
+        const int T = (int)min<size_t>(n_todo, (size_t)threads);
         auto work = [&](int t) {
-            for (size_t i = (size_t)t; i < blocks.size(); i += (size_t)T) {
+            for (size_t j = (size_t)t; j < n_todo; j += (size_t)T) {
+                const size_t i = all ? j : (size_t)todo[j];
                 const Block& k = blocks[i];
                 if (!inflate_block(src + (k.file_off - src_off), k.len, k.isize, dst + at[i])) {
                     int64_t cur = bad.load();
@@ -322,8 +387,8 @@ uint32_t BamReader::fill(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint6
                 }
             }
         };
-        if (T <= 1) work(0);
-        else parallel_run(T, work);
+        if (T == 1) work(0);
+        else if (T > 1) parallel_run(T, work);
         if (bad.load() >= 0) {
             err_ = "BAM input: the BGZF block at file offset " + to_string(bad.load()) + " has a bad CRC or size";
             return 0;
@@ -345,6 +410,7 @@ struct BamAll {
     vector<uint64_t> rec, off{0};
     string names, err, warn;
     uint32_t batches = 0;
+    uint64_t on_device = 0, refused = 0;
 };
 }  // namespace
 
@@ -352,8 +418,16 @@ extern "C" {
 int fplh_is_bam(const char* path) { return fplh::is_bam_file(path) ? 1 : 0; }
 
 void* fplh_bam_read_all(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes) {
+    return fplh_bam_read_all_with(path, chunk_bytes, max_reads, window_bytes, nullptr, nullptr);
+}
+uint64_t fplh_bam_all_device(void* h) { return ((BamAll*)h)->on_device; }
+uint64_t fplh_bam_all_refused(void* h) { return ((BamAll*)h)->refused; }
+
+void* fplh_bam_read_all_with(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes, fplh::BgzfInflateFn fn,
+                             void* user) {
     fplh::BamReader rd(path);
     if (!rd.ok()) return nullptr;
+    rd.set_inflater(fn, user);
     if (window_bytes) rd.set_window_bytes(window_bytes);
     BamAll* a = new BamAll;
     for (;;) {
@@ -372,6 +446,8 @@ void* fplh_bam_read_all(const char* path, uint64_t chunk_bytes, uint32_t max_rea
     }
     a->err = rd.error();
     a->warn = rd.warning();
+    a->on_device = rd.blocks_on_device();
+    a->refused = rd.blocks_refused();
     return a;
 }
 uint32_t fplh_bam_all_n(void* h) { return (uint32_t)((BamAll*)h)->rec.size(); }

@@ -3,7 +3,8 @@
  *
  * A BAM is BGZF: gzip members of at most 64 KiB of output, each of which says in its header how long it is (BSIZE) and in its
  * trailer how much it inflates to (ISIZE).  The reader streams the file in windows of blocks, inflates a window's blocks side
- * by side on the worker pool straight into the batch's (page-locked) record buffer, and walks the records on one thread --
+ * by side on the worker pool -- or hands the window to an inflater (set_inflater: the device, csrc/bgzf_inflate.h) and inflates
+ * only what that refuses -- straight into the batch's (page-locked) record buffer, and walks the records on one thread --
  * about 24 bytes of each: block_size, the name, flag and l_seq.  The bases and qualities are never touched on the host: the
  * device decodes them (fpl_process_bam_async, fastplong_amd/csrc/bam_decode.h).
  *
@@ -27,6 +28,12 @@ namespace fplh {
 /* gzip magic, a BGZF "BC" extra field, and "BAM\1" at the start of the inflated bytes */
 bool is_bam_file(const std::string& path);
 
+/* An inflater the reader may hand its windows to: the C-ABI's fpl_inflate_bgzf with its handle as `user` (the host library does not
+ * link the device library; the CLI looks the call up).  comp / blocks / out as for that call; returns 0 when it ran -- blocks[i].status
+ * then says which blocks it vouches for (0) --, anything else when it could not. */
+typedef int (*BgzfInflateFn)(void* user, const uint8_t* comp, uint64_t comp_bytes, fpl_bgzf_block* blocks, uint32_t n_blocks, uint8_t* out,
+                             uint64_t out_bytes);
+
 class BamReader {
    public:
     explicit BamReader(const std::string& path);
@@ -45,6 +52,20 @@ class BamReader {
     uint64_t compressed_pulled() const { return comp_end_; } /* file bytes of the blocks inflated so far */
     uint64_t file_size() const { return file_size_; }
     uint64_t records_seen() const { return rec_no_; } /* records walked, skipped ones included */
+    /* With an inflater set, a window is everything the batch still takes, read into page-locked memory and handed to fn in one
+       call.  Every block fn does not vouch for -- and every block, when fn fails -- is inflated by the host as without an inflater:
+       the host's verdict on a block is the verdict, and the error texts are the same.  fn == nullptr: the host path alone. */
+    void set_inflater(BgzfInflateFn fn, void* user) {
+        if ((fn != nullptr) != (inflate_fn_ != nullptr)) { /* the file bytes in hand lie in the other buffer: read again */
+            comp_.clear();
+            pin_comp_.clear();
+            comp_off_ = comp_end_;
+        }
+        inflate_fn_ = fn;
+        inflate_user_ = user;
+    }
+    uint64_t blocks_on_device() const { return dev_blocks_; }     /* blocks the inflater vouched for */
+    uint64_t blocks_refused() const { return refused_blocks_; }   /* blocks it was given and the host inflated again */
     /* test hook: inflated bytes per window (default 8 MiB; at least one block is always taken) */
     void set_window_bytes(uint64_t w) { window_ = w ? w : 1; }
 
@@ -55,7 +76,10 @@ class BamReader {
         uint32_t isize;
     };
     bool next_blocks(uint64_t want, std::vector<Block>& out); /* the blocks of the next window (false: error) */
-    bool read_comp(uint64_t off, uint64_t len);               /* comp_ holds file bytes [comp_off_, comp_off_ + comp_.size()) */
+    bool read_comp(uint64_t off, uint64_t len);               /* the buffer holds file bytes [comp_off_, comp_off_ + comp_size()) */
+    /* the file bytes in hand: comp_, or with an inflater pin_comp_ (page-locked: the inflater's upload reads it in place) */
+    const uint8_t* comp_data() const { return inflate_fn_ ? pin_comp_.data() : comp_.data(); }
+    uint64_t comp_size() const { return inflate_fn_ ? pin_comp_.size() : comp_.size(); }
     bool walk(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint64_t max_bases, uint32_t& got);
     int fd_ = -1;
     std::string path_, err_, warn_;
@@ -71,6 +95,11 @@ class BamReader {
     bool last_was_eof_block_ = false;
     bool done_ = false;
     uint64_t rec_no_ = 0;
+    BgzfInflateFn inflate_fn_ = nullptr;
+    void* inflate_user_ = nullptr;
+    ByteBuf pin_comp_;                     /* with an inflater: what comp_ is without one, in page-locked memory */
+    std::vector<fpl_bgzf_block> dev_desc_; /* its descriptors */
+    uint64_t dev_blocks_ = 0, refused_blocks_ = 0;
 };
 
 }  // namespace fplh
@@ -80,6 +109,11 @@ int fplh_is_bam(const char* path);
 /* test hook: the whole file through BamReader with batches of chunk_bytes / max_reads and windows of window_bytes.  Returns a
    handle (fplh_bam_all_*), NULL when the file cannot be opened; the error and warning texts are in the handle. */
 void* fplh_bam_read_all(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes);
+/* the same with an inflater (BamReader::set_inflater); fplh_bam_all_device / _refused: the reader's two block counts */
+void* fplh_bam_read_all_with(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes, fplh::BgzfInflateFn fn,
+                             void* user);
+uint64_t fplh_bam_all_device(void* h);
+uint64_t fplh_bam_all_refused(void* h);
 uint32_t fplh_bam_all_n(void* h);          /* records emitted */
 uint32_t fplh_bam_all_batches(void* h);    /* batches they came in */
 const uint8_t* fplh_bam_all_bytes(void* h, uint64_t* n); /* each batch's record bytes, back to back */

@@ -85,7 +85,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""},
 };
 
 struct Args {
@@ -465,7 +465,12 @@ int main(int argc, char* argv[]) {
     typedef int (*BamAsyncFn)(fpl_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*,
                               fpl_read_result*);
     typedef int (*BamDecodeFn)(int32_t, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*);
+    typedef void* (*InflaterCreateFn)(int32_t);
+    typedef void (*InflaterDestroyFn)(void*);
     BamAsyncFn bamAsync = nullptr;
+    fplh::BgzfInflateFn bgzfInflate = nullptr;
+    InflaterDestroyFn inflaterDestroy = nullptr;
+    void* inflater = nullptr;
     if (bamIn) {
         bamAsync = (BamAsyncFn)dlsym(RTLD_DEFAULT, "fpl_process_bam_async");
         BamDecodeFn bamDecode = (BamDecodeFn)dlsym(RTLD_DEFAULT, "fpl_decode_bam");
@@ -473,6 +478,16 @@ int main(int argc, char* argv[]) {
             error_exit("BAM input needs fpl_process_bam_async and fpl_decode_bam (C-ABI version 8), which the loaded libfastplong_amd.so lacks");
         fplh::set_bam_decoder([bamDecode](const uint8_t* bam, uint64_t nb, const uint64_t* rec, const uint64_t* of, uint32_t n, uint8_t* sq,
                                           uint8_t* ql) { return bamDecode(0, bam, nb, rec, of, n, sq, ql) == FPL_OK; });
+        /* --device_inflate: the BGZF blocks are inflated on the first device (fpl_inflate_bgzf; the ABI version is still 10, the
+           three calls are found by name), by the reader of the evaluation prefix and by the main one.  A library without them:
+           the host inflates, silently, as for the calls of v10. */
+        if (cmd.exist("device_inflate")) {
+            InflaterCreateFn mk = (InflaterCreateFn)dlsym(RTLD_DEFAULT, "fpl_inflater_create");
+            bgzfInflate = (fplh::BgzfInflateFn)dlsym(RTLD_DEFAULT, "fpl_inflate_bgzf");
+            inflaterDestroy = (InflaterDestroyFn)dlsym(RTLD_DEFAULT, "fpl_inflater_destroy");
+            if (mk && bgzfInflate && inflaterDestroy) inflater = mk(0);
+            if (inflater) fplh::set_bam_inflater(bgzfInflate, inflater);
+        }
     }
     if (!fromStdin && in != "/dev/stdin") {
         fplh::Batch b;
@@ -674,6 +689,7 @@ int main(int argc, char* argv[]) {
     if (bamIn) {
         bamReader = new fplh::BamReader(in);
         if (!bamReader->ok()) error_exit("Failed to open file: " + in);
+        if (inflater) bamReader->set_inflater(bgzfInflate, inflater);
     } else if (!chunked) {
         reader = new fplh::FastqReader(in);
         if (!reader->ok()) error_exit("Failed to open file: " + in);
@@ -1370,6 +1386,12 @@ int main(int argc, char* argv[]) {
             cerr << "device thread " << d << ": " << nSubmit[d] << " submissions " << tSubmit[d] << " s (mean depth behind them "
                  << (nSubmit[d] ? (double)depthSum[d] / (double)nSubmit[d] : 0.0) << "), queue empty with room for a batch " << nMiss[d]
                  << " times, nothing in flight and nothing parsed " << tStarved[d] << " s" << endl;
+    if (cmd.exist("verbose") && inflater && bamReader) {
+        uint64_t onDev = 0, refused = 0;
+        fplh::bam_prefix_block_counts(onDev, refused);
+        cerr << "input: BGZF blocks inflated on the device: " << onDev + bamReader->blocks_on_device() << " ("
+             << refused + bamReader->blocks_refused() << " refused, inflated by the host)" << endl;
+    }
     if (cmd.exist("verbose") && devBamGz)
         cerr << "device gzip: " << nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
     if (cmd.exist("verbose") && textMode) {
@@ -1472,6 +1494,7 @@ int main(int argc, char* argv[]) {
     if (getenv("FPLH_TEARDOWN_TIMING")) { /* measurement hook: what the explicit teardown would cost */
         const double a = now();
         for (auto& d : dev) fpl_destroy(d.ctx);
+        if (inflater) inflaterDestroy(inflater);
         cerr << "teardown: contexts " << now() - a << " s" << endl;
     }
     /* every output has been written, flushed and closed above; skip the static destructors (worker pool, HIP runtime) */

@@ -178,9 +178,29 @@ long read_prefix(FastqReader& reader, Batch& b, long read_limit, long base_limit
 static BamDecoder g_bam_decoder;
 void set_bam_decoder(BamDecoder f) { g_bam_decoder = std::move(f); }
 
+static BgzfInflateFn g_bam_inflate = nullptr;
+static void* g_bam_inflate_user = nullptr;
+static uint64_t g_prefix_on_device = 0, g_prefix_refused = 0;
+void set_bam_inflater(BgzfInflateFn fn, void* user) {
+    g_bam_inflate = fn;
+    g_bam_inflate_user = user;
+}
+void bam_prefix_block_counts(uint64_t& on_device, uint64_t& refused) {
+    on_device = g_prefix_on_device;
+    refused = g_prefix_refused;
+}
+
 long read_bam_prefix(const string& path, Batch& b, long read_limit, long base_limit) {
     BamReader rd(path);
     if (!rd.ok()) return 0;
+    rd.set_inflater(g_bam_inflate, g_bam_inflate_user);
+    struct Count { /* whichever way this function is left */
+        BamReader& r;
+        ~Count() {
+            g_prefix_on_device += r.blocks_on_device();
+            g_prefix_refused += r.blocks_refused();
+        }
+    } count{rd};
     b.clear();
     /* the first record alone (where the reference's count of bytes starts), then the rest of the prefix */
     if (rd.fill(b, ~0ull, 1) == 0) {

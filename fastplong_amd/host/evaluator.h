@@ -16,6 +16,8 @@
 #include <functional>
 #include <string>
 
+#include "fastplong_amd.h"
+
 namespace fplh {
 
 /* The counting loops of the detection (src/evaluator.cpp:300-345) over the first / last 128 positions of every read of the
@@ -43,6 +45,10 @@ void set_adapter_picker(AdapterPicker f);
  * host has no decoder of its own: without one, a BAM input cannot be evaluated and the process ends with an error. */
 using BamDecoder = std::function<bool(const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*)>;
 void set_bam_decoder(BamDecoder f);
+/* ... and its BGZF blocks may be inflated by this call (host/bam.h: BamReader::set_inflater; the CLI: the C-ABI's fpl_inflate_bgzf
+ * and its handle); the counts are the blocks the prefix readers had inflated that way / had to inflate again */
+void set_bam_inflater(int (*fn)(void*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t, uint8_t*, uint64_t), void* user);
+void bam_prefix_block_counts(uint64_t& on_device, uint64_t& refused);
 class BamReader;
 struct Batch;
 /* up to read_limit records / base_limit bases of a BAM input, decoded (b: a CSR batch afterwards); the read-count estimate

@@ -436,6 +436,49 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
 int fpl_set_bam_gzip(fpl_ctx* ctx, int on);
 int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len);
 
+/*
+ * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
+ * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
+ * caller then inflates on the host.
+ *
+ * The inflater is a handle of its own, not part of a context: the evaluation prefix of a BAM input is read before any fpl_ctx
+ * exists (as for fpl_decode_bam).  It owns one stream and its device buffers, which grow with headroom and never shrink.
+ *
+ *   fpl_inflater_create   NULL when the device cannot be used.
+ *   fpl_inflate_bgzf      comp[0 .. comp_bytes) holds the blocks' raw deflate payloads (what lies between a block's gzip header and
+ *                         its 8-byte trailer), blocks[i] says where payload i is (comp_off, comp_len <= 16 MiB), where its output
+ *                         goes (out_off, isize <= 65536) and what the trailer says (isize, crc32).  Every range is checked on the
+ *                         calling thread first: a range outside comp / out is FPL_ERR_ARG and nothing is enqueued.  One call
+ *                         uploads comp and the descriptors, launches ONE kernel (a wave per block) and brings back the output
+ *                         ranges of the blocks -- bytes of out between them are not touched -- and blocks[i].status.  Synchronous.
+ *                         Page-locked comp and out (fpl_host_alloc) are recommended; pageable memory works.  n_blocks == 0: FPL_OK,
+ *                         nothing done.  Thread-compatible: one call at a time per handle.
+ *   status                FPL_BGZF_OK: out[out_off .. out_off + isize) is the block's data, size and CRC-32 agree with the trailer.
+ *                         Anything else: REFUSED -- the bytes of that range are undefined and the caller inflates the block itself;
+ *                         the device never has the last word on a bad block.  The kernel refuses whatever it does not vouch for
+ *                         (docs/kernels.md), among it streams zlib accepts: a distance code of a single 1-bit code.
+ */
+typedef struct fpl_bgzf_block { /* 32 bytes */
+    uint64_t comp_off;
+    uint64_t out_off;
+    uint32_t comp_len;
+    uint32_t isize;
+    uint32_t crc32;
+    uint32_t status; /* out */
+} fpl_bgzf_block;
+enum {
+    FPL_BGZF_OK = 0,
+    FPL_BGZF_MALFORMED = 1, /* not a deflate stream this kernel decodes */
+    FPL_BGZF_SIZE = 2,      /* more or fewer bytes than isize */
+    FPL_BGZF_CRC = 3,       /* the bytes' CRC-32 is not the trailer's */
+    FPL_BGZF_OVERRUN = 4    /* the stream goes on behind comp_len */
+};
+typedef struct fpl_inflater fpl_inflater;
+fpl_inflater* fpl_inflater_create(int32_t device);
+int fpl_inflate_bgzf(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes, fpl_bgzf_block* blocks, uint32_t n_blocks, uint8_t* out,
+                     uint64_t out_bytes);
+void fpl_inflater_destroy(fpl_inflater* inf);
+
 /* Page-locked host memory for the arrays handed to fpl_process_batch[_async] / fpl_process_text_async: the DMA engines read it
  * directly.  Blocks of 8 MB and more are anonymous memory on transparent huge pages, touched and registered with the runtime
  * (hipHostRegister, portable across devices) -- locking 4 KB pages goes at 4 GB/s, 370 huge pages take 13 ms for 740 MB; smaller

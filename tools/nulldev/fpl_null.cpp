@@ -284,6 +284,12 @@ int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     *gz_len = 0;
     return fpl_wait(ctx);
 }
+/* (BGZF inflate: no device, so no inflater -- a host that finds the calls gets no handle and inflates itself) */
+fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
+int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
+    return n_blocks ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
+void fpl_inflater_destroy(fpl_inflater*) {}
 int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return FPL_ERR_ARG;
     *out = 0;
