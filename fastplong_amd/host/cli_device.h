@@ -1,0 +1,87 @@
+/*
+ * cli_device.h -- what the CLI needs from libfastplong_amd.so beyond the calls it links against: the optional entry points
+ * of the later C-ABI versions, looked up by name, and the device contexts.  Part of cli.cpp's translation unit.
+ */
+#ifndef FPLH_CLI_DEVICE_H
+#define FPLH_CLI_DEVICE_H
+
+#include "bam.h"
+#include "cli_options.h"
+
+/* The optional entry points.  They are looked up at run time: the binary must start against a library without them (the
+   test stand-ins, an older build).  Which of them a run NEEDS is the caller's business: BAM input without the two v8 calls
+   is an error (evaluate_input), a missing gzip or inflater call leaves that work on the host without a word. */
+struct DeviceApi {
+    typedef int (*BamAsyncFn)(fpl_ctx*, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*,
+                              fpl_read_result*);
+    typedef int (*BamDecodeFn)(int32_t, const uint8_t*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint8_t*, uint8_t*);
+    typedef void* (*InflaterCreateFn)(int32_t);
+    typedef void (*InflaterDestroyFn)(void*);
+    typedef int (*SetGzipFn)(fpl_ctx*, int);
+    typedef int (*WaitTextGzFn)(fpl_ctx*, fpl_text_result*, const fpl_read_result**, const uint32_t**, const uint8_t**, uint64_t*);
+    typedef int (*WaitBamGzFn)(fpl_ctx*, const uint8_t**, uint64_t*);
+    /* BAM input, C-ABI version 8 */
+    BamAsyncFn process_bam_async = nullptr;
+    BamDecodeFn decode_bam = nullptr;
+    /* --device_inflate (the ABI version is still 10, the three calls are found by name) */
+    InflaterCreateFn inflater_create = nullptr;
+    fplh::BgzfInflateFn inflate_bgzf = nullptr;
+    InflaterDestroyFn inflater_destroy = nullptr;
+    /* --out *.gz deflated on the device: text batches (version 9), BAM-backed batches (version 10) */
+    SetGzipFn set_text_gzip = nullptr;
+    WaitTextGzFn wait_text_gz = nullptr;
+    SetGzipFn set_bam_gzip = nullptr;
+    WaitBamGzFn wait_bam_gz = nullptr;
+};
+
+static DeviceApi load_device_api() {
+    DeviceApi a;
+    a.process_bam_async = (DeviceApi::BamAsyncFn)dlsym(RTLD_DEFAULT, "fpl_process_bam_async");
+    a.decode_bam = (DeviceApi::BamDecodeFn)dlsym(RTLD_DEFAULT, "fpl_decode_bam");
+    a.inflater_create = (DeviceApi::InflaterCreateFn)dlsym(RTLD_DEFAULT, "fpl_inflater_create");
+    a.inflate_bgzf = (fplh::BgzfInflateFn)dlsym(RTLD_DEFAULT, "fpl_inflate_bgzf");
+    a.inflater_destroy = (DeviceApi::InflaterDestroyFn)dlsym(RTLD_DEFAULT, "fpl_inflater_destroy");
+    a.set_text_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_text_gzip");
+    a.wait_text_gz = (DeviceApi::WaitTextGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_text_gz");
+    a.set_bam_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_gzip");
+    a.wait_bam_gz = (DeviceApi::WaitBamGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_bam_gz");
+    return a;
+}
+
+/* a gzip form on every context or on none: one context that refuses switches all of them back off (`have_wait`: the wait
+   call that fetches the members exists too) */
+static bool enable_on_all(DeviceApi::SetGzipFn set, bool have_wait, const vector<fpl_ctx*>& ctxs) {
+    bool on = set && have_wait;
+    for (size_t d = 0; on && d < ctxs.size(); d++)
+        if (set(ctxs[d], 1) != FPL_OK) on = false;
+    if (!on)
+        for (size_t d = 0; set && d < ctxs.size(); d++) (void)set(ctxs[d], 0);
+    return on;
+}
+
+/* one context per device (and, in the pipeline, one host thread) */
+static vector<fpl_ctx*> create_contexts(const Options& opt) {
+    const int nGpus = opt.nGpus;
+    vector<fpl_adapter> fa(opt.fasta.size());
+    for (size_t i = 0; i < opt.fasta.size(); i++) fa[i] = fpl_adapter{opt.fasta[i].data(), (int32_t)opt.fasta[i].size()};
+    vector<fpl_ctx*> ctxs((size_t)nGpus, nullptr);
+    /* (a context costs a tenth of a second -- streams, events, tables, the device's first allocations: the devices' contexts
+       are made side by side, a node's eight in the time of one) */
+    vector<int> rcs((size_t)nGpus, FPL_OK);
+    auto make = [&](int d) {
+        rcs[(size_t)d] = fpl_create(&ctxs[(size_t)d], &opt.o, opt.startAd.data(), (int32_t)opt.startAd.size(), opt.endAd.data(),
+                                    (int32_t)opt.endAd.size(), fa.data(), (int32_t)fa.size(), d, 65536);
+    };
+    vector<thread> makers;
+    for (int d = 1; d < nGpus; d++) makers.emplace_back(make, d);
+    make(0);
+    for (auto& t : makers) t.join();
+    for (int d = 0; d < nGpus; d++) {
+        if (rcs[(size_t)d] == FPL_ERR_NO_DEVICE)
+            error_exit("fastplong_amd needs " + to_string(nGpus) + " HIP device(s); there is no CPU path");
+        if (rcs[(size_t)d] != FPL_OK) error_exit(string("fpl_create: ") + fpl_strerror(rcs[(size_t)d]));
+    }
+    return ctxs;
+}
+
+#endif

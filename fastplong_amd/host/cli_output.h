@@ -1,0 +1,125 @@
+/*
+ * cli_output.h -- the files a run writes its reads to: --out, --failed_out, or --split*'s numbered files.
+ * Part of cli.cpp's translation unit.
+ */
+#ifndef FPLH_CLI_OUTPUT_H
+#define FPLH_CLI_OUTPUT_H
+
+#include "cli_options.h"
+#include "fastq.h"
+
+/* Outputs are plain files; a name ending in .gz gets gzip members (-z level), one per formatted slice,
+   deflated on the formatter threads and concatenated by the writer: any gzip reader takes that as one stream */
+struct OutFile {
+    FILE* f = nullptr;
+    bool gz = false;
+    bool wrote = false;
+    /* FPLH_PARALLEL_WRITE (measurement hook): the pieces of a batch written side by side at their offsets (pwrite from
+       the worker pool; nothing goes through the FILE's buffer then).  Measured on the GPU box into tmpfs: no gain -- one
+       thread copies into the page cache at 5.5-6 GB/s, fifteen pwrite()s side by side, or fifteen memcpy()s into a mapped
+       window of the file, fill it at the same 5.5-6 GB/s: what bounds a single output file is the kernel's insertion of
+       fresh pages into that file's page cache, not the copy.  So the plain path stays the default. */
+    bool positional = false;
+    uint64_t pos = 0;
+    explicit operator bool() const { return f != nullptr; }
+
+    static OutFile open(const string& path) {
+        OutFile o;
+        if (path.empty()) return o;
+        o.gz = ends_with_gz(path);
+        o.f = fopen(path.c_str(), "wb");
+        if (!o.f) error_exit("Failed to write: " + path);
+        struct stat st;
+        o.positional = getenv("FPLH_PARALLEL_WRITE") && fstat(fileno(o.f), &st) == 0 && S_ISREG(st.st_mode);
+        return o;
+    }
+    void write_pieces(const vector<string>& pieces) {
+        if (positional) { /* input order by construction: the offsets are the running sum of the pieces' sizes */
+            vector<uint64_t> at(pieces.size());
+            for (size_t i = 0; i < pieces.size(); i++) {
+                at[i] = pos;
+                pos += pieces[i].size();
+                if (!pieces[i].empty()) wrote = true;
+            }
+            std::atomic<bool> bad{false};
+            const int fd = fileno(f);
+            fplh::parallel_run((int)pieces.size(), [&](int i) {
+                const char* p = pieces[i].data();
+                size_t left = pieces[i].size();
+                uint64_t off = at[i];
+                while (left > 0) {
+                    const ssize_t w = pwrite(fd, p, left, (off_t)off);
+                    if (w < 0 && errno == EINTR) continue;
+                    if (w <= 0) {
+                        bad = true;
+                        return;
+                    }
+                    p += w;
+                    off += (uint64_t)w;
+                    left -= (size_t)w;
+                }
+            });
+            if (bad) error_exit("write failed");
+            return;
+        }
+        for (auto& piece : pieces)
+            if (!piece.empty()) {
+                if (fwrite(piece.data(), 1, piece.size(), f) != piece.size()) error_exit("write failed");
+                wrote = true;
+            }
+    }
+    void close(int gzLevel) {
+        if (!f) return;
+        if (gz && !wrote) { /* an empty .gz still has to be a gzip stream */
+            const string e = fplh::gzip_member(string(), gzLevel);
+            if (fwrite(e.data(), 1, e.size(), f) != e.size()) error_exit("write failed");
+        }
+        /* the buffered tail goes out here: a full disk shows up as a failing flush / close */
+        if (f == stdout ? (fflush(stdout) != 0 || ferror(stdout)) : (fclose(f) != 0)) error_exit("write failed");
+    }
+};
+
+struct Outputs {
+    OutFile fout, ffail;
+    int gzLevel = 4;
+    fplh::SplitOutput* split = nullptr; /* --split / --split_by_lines: the workers' private writers take the passing reads */
+    bool gatherOut = false;             /* --out is written as gather lists over the batches' own arrays (build_gather) */
+
+    bool any_gz() const { return (fout && fout.gz) || (ffail && ffail.gz); }
+    void gzip_pieces(vector<string>& pieces) const { /* in parallel; pieces stay below 4 GiB (one slice of a batch) */
+        const int level = gzLevel;
+        fplh::parallel_run((int)pieces.size(), [&](int i) {
+            if (!pieces[i].empty()) fplh::gzip_into(pieces[i], level, pieces[i]);
+        });
+    }
+    void close() {
+        fout.close(gzLevel);
+        ffail.close(gzLevel);
+    }
+};
+
+static Outputs open_outputs(const Options& opt) {
+    Outputs o;
+    /* with --split* the reference never calls initOutput (src/seprocessor.cpp:65-67): no single --out file and no
+       --failed_out either; the workers' private writers take the passing reads */
+    o.fout = OutFile::open(opt.splitEnabled ? string() : opt.out);
+    o.ffail = OutFile::open(opt.splitEnabled ? string() : opt.failedOut);
+    if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.positional = false;
+    o.gzLevel = min(9, max(1, opt.compression));
+    if (opt.splitEnabled)
+        o.split = new fplh::SplitOutput(opt.out, opt.splitDigits, opt.workers, opt.splitByLines, opt.splitNumber, opt.splitSize, o.gzLevel);
+    /* Plain --out alone that is NOT a regular file -- a pipe into an aligner or a compressor (--stdout, /dev/stdout), /dev/null --
+       is written as gather lists over the batches' own arrays (build_gather): nothing is formatted.  Into a regular file the
+       one writer thread's copy into the page cache is the bottleneck either way (18 GB: 2.9 s from formatted pieces, 3.6 s
+       from eight small entries per read), so files keep the pieces the formatter threads put together side by side.
+       FPLH_NO_GATHER / FPLH_GATHER_FILES: measurement hooks */
+    o.gatherOut = o.fout && !o.fout.gz && !o.ffail && !opt.fragmentMode && !o.split && !getenv("FPLH_NO_GATHER");
+    if (o.gatherOut && !getenv("FPLH_GATHER_FILES")) {
+        struct stat ost;
+        if (fstat(fileno(o.fout.f), &ost) == 0 && S_ISREG(ost.st_mode)) o.gatherOut = false;
+    }
+    if (o.gatherOut) fflush(o.fout.f); /* (from here on the descriptor is written directly) */
+    return o;
+}
+
+#endif
