@@ -155,6 +155,12 @@ FRAGMENT_DTYPE = [
 ]
 REGION_DTYPE = [("start", "<u4"), ("len", "<u4")]
 
+# struct fpl_gzip_window (32 bytes): the result of fpl_inflate_gzip; status: FPL_GZIP_*
+GZIP_WINDOW_DTYPE = [("out_bytes", "<u8"), ("end_bit", "<u8"), ("status", "<u4"), ("crc32", "<u4"), ("final_block", "<u4"), ("chunks", "<u4")]
+FPL_GZIP_OK = 0
+FPL_GZIP_MALFORMED = 1
+FPL_GZIP_ROOM = 2
+FPL_GZIP_OVERRUN = 3
 # struct fpl_bgzf_block (32 bytes): one BGZF block of fpl_inflate_bgzf; status: FPL_BGZF_*
 BGZF_BLOCK_DTYPE = [("comp_off", "<u8"), ("out_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("status", "<u4")]
 FPL_BGZF_OK = 0

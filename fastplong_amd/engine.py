@@ -26,7 +26,7 @@ EXPORTS = [
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
-    "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy",
+    "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
 ]
 
 
@@ -158,6 +158,10 @@ def load_library(path=None):
         L.fpl_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
         L.fpl_inflater_destroy.restype = None
         L.fpl_inflater_destroy.argtypes = [C.c_void_p]
+    if hasattr(L, "fpl_inflate_gzip"):
+        L.fpl_inflate_gzip.restype = C.c_int
+        L.fpl_inflate_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                       C.c_uint32, C.c_void_p]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -209,6 +213,22 @@ class Inflater:
         if rc != abi.FPL_OK:
             raise FplError("fpl_inflate_bgzf: %s" % self.L.fpl_strerror(rc).decode())
         return out, blk["status"].copy()
+
+    def inflate_gzip(self, comp, start_bit=0, zdict=b"", out_cap=0, chunk_bytes=0):
+        """One window of a member's raw deflate payload through fpl_inflate_gzip: comp (bytes), the bit offset of a block start
+        in it, the up to 32 KiB in front of that point.  -> (rc, a record of abi.GZIP_WINDOW_DTYPE, the bytes); rc != 0: the call
+        refused its arguments or failed, nothing else is meaningful."""
+        if not hasattr(self.L, "fpl_inflate_gzip"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_inflate_gzip")
+        comp = np.frombuffer(bytes(comp), np.uint8)
+        zd = np.frombuffer(bytes(zdict), np.uint8)
+        out = np.zeros(int(out_cap), np.uint8)
+        res = np.zeros(1, np.dtype(abi.GZIP_WINDOW_DTYPE))
+        rc = self.L.fpl_inflate_gzip(self.h, comp.ctypes.data if len(comp) else None, len(comp), int(start_bit), zd.ctypes.data if len(zd) else None,
+                                     len(zd), out.ctypes.data if len(out) else None, len(out), int(chunk_bytes), res.ctypes.data)
+        r = res[0]
+        ok = rc == abi.FPL_OK and r["status"] == abi.FPL_GZIP_OK
+        return rc, r, out[:int(r["out_bytes"])].tobytes() if ok else b""
 
     def close(self):
         if self.h:

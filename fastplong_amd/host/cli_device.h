@@ -7,6 +7,7 @@
 
 #include "bam.h"
 #include "cli_options.h"
+#include "fastq.h"
 
 /* The optional entry points.  They are looked up at run time: the binary must start against a library without them (the
    test stand-ins, an older build).  Which of them a run NEEDS is the caller's business: BAM input without the two v8 calls
@@ -27,6 +28,7 @@ struct DeviceApi {
     InflaterCreateFn inflater_create = nullptr;
     fplh::BgzfInflateFn inflate_bgzf = nullptr;
     InflaterDestroyFn inflater_destroy = nullptr;
+    fplh::GzipInflateFn inflate_gzip = nullptr; /* (the same handle: a one-member .gz, host/fastq.h) */
     /* --out *.gz deflated on the device: text batches (version 9), BAM-backed batches (version 10) */
     SetGzipFn set_text_gzip = nullptr;
     WaitTextGzFn wait_text_gz = nullptr;
@@ -41,6 +43,7 @@ static DeviceApi load_device_api() {
     a.inflater_create = (DeviceApi::InflaterCreateFn)dlsym(RTLD_DEFAULT, "fpl_inflater_create");
     a.inflate_bgzf = (fplh::BgzfInflateFn)dlsym(RTLD_DEFAULT, "fpl_inflate_bgzf");
     a.inflater_destroy = (DeviceApi::InflaterDestroyFn)dlsym(RTLD_DEFAULT, "fpl_inflater_destroy");
+    a.inflate_gzip = (fplh::GzipInflateFn)dlsym(RTLD_DEFAULT, "fpl_inflate_gzip");
     a.set_text_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_text_gzip");
     a.wait_text_gz = (DeviceApi::WaitTextGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_text_gz");
     a.set_bam_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_gzip");

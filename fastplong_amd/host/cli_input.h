@@ -13,7 +13,7 @@
 struct InputFacts {
     bool bam = false;         /* BAM input (host/bam.h): recognised by its content; its bases are decoded on the device */
     bool isRNA = false;
-    void* inflater = nullptr; /* --device_inflate: the first device's BGZF inflater (fpl_inflater_create), or none */
+    void* inflater = nullptr; /* --device_inflate: the first device's inflater (fpl_inflater_create) for BGZF blocks or a one-member .gz, or none */
 };
 
 /* The evaluation of the input's first reads: Evaluator::evaluateSeqLenAndCheckRNA (src/evaluator.cpp:16-61: U vs T in the
@@ -35,6 +35,18 @@ static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
             if (api.inflater_create && api.inflate_bgzf && api.inflater_destroy) in.inflater = api.inflater_create(0);
             if (in.inflater) fplh::set_bam_inflater(api.inflate_bgzf, in.inflater);
         }
+    }
+    /* --device_inflate on a gzip FILE: the single-member lane of the in-memory expansion hands its member to the first device
+       window by window (fpl_inflate_gzip; host/fastq.h set_gzip_inflater).  The multi-member lane, --gz_stream and pipes never
+       come near it.  A library without the call: the host inflates, silently. */
+    if (opt.deviceInflate && !in.bam && !opt.from_stdin && !opt.gzStream && api.inflater_create && api.inflate_gzip && api.inflater_destroy) {
+        unsigned char magic[2] = {0, 0};
+        if (FILE* f = fopen(opt.in.c_str(), "rb")) {
+            if (fread(magic, 1, 2, f) != 2) magic[0] = 0;
+            fclose(f);
+        }
+        if (magic[0] == 0x1f && magic[1] == 0x8b) in.inflater = api.inflater_create(0);
+        if (in.inflater) fplh::set_gzip_inflater(api.inflate_gzip, in.inflater);
     }
     if (!opt.from_stdin) {
         fplh::Batch b;
@@ -149,6 +161,10 @@ static void expand_gzip_input(InputPlan& p, const Options& opt) {
         munmap((void*)p.chunkMem, (size_t)reserved);
         p.chunkMem = nullptr;
     }
+    uint64_t dev_windows = 0, dev_refused = 0;
+    fplh::gzip_inflater_counts(&dev_windows, &dev_refused);
+    if (dev_windows && opt.verbose)
+        cerr << "input: gzip member inflated on the device: " << dev_windows << " windows (" << dev_refused << " refused, inflated by the host)" << endl;
     if (!p.chunkMem && opt.verbose)
         cerr << "input: gzip text not expanded in memory (" << now_s() - t0 << " s spent finding out): the sequential reader streams it" << endl;
     if (p.chunkMem) { /* (the mapping lives until the process ends) */

@@ -386,6 +386,127 @@ std::atomic<uint64_t> GzMembers::delivered{0};
  * The member's trailer gives its inflated size modulo 4 GiB; the candidates size, size + 4 GiB, ... are tried in turn (a
  * wrong one fails with "no space" at the end of the output).  nullptr: not a single clean member, no libdeflate, or more
  * text than max_bytes. */
+static GzipInflateFn g_gzip_inflate = nullptr;
+static void* g_gzip_inflate_user = nullptr;
+static uint64_t g_gzip_window = 32ull << 20;
+static std::atomic<uint64_t> g_gzip_windows{0}, g_gzip_refused{0};
+void set_gzip_inflater(GzipInflateFn fn, void* user, uint64_t window_bytes) {
+    g_gzip_inflate = fn;
+    g_gzip_inflate_user = user;
+    g_gzip_window = window_bytes ? window_bytes : 32ull << 20;
+}
+void gzip_inflater_counts(uint64_t* windows, uint64_t* refused) {
+    *windows = g_gzip_windows.exchange(0);
+    *refused = g_gzip_refused.exchange(0);
+}
+
+/* where the deflate payload of the gzip member at in[0 .. n) starts (RFC 1952: FEXTRA, FNAME, FCOMMENT, FHCRC); 0: no such header */
+static size_t gzip_payload_start(const unsigned char* in, size_t n) {
+    if (n < 18 || in[0] != 0x1f || in[1] != 0x8b || in[2] != 8 || (in[3] & 0xE0)) return 0;
+    const unsigned flg = in[3];
+    size_t p = 10;
+    if (flg & 4) {
+        if (p + 2 > n) return 0;
+        p += 2 + ((size_t)in[p] | ((size_t)in[p + 1] << 8));
+    }
+    for (unsigned bit : {8u, 16u})
+        if (flg & bit) {
+            while (p < n && in[p]) p++;
+            p++;
+        }
+    if (flg & 2) p += 2;
+    return p + 8 <= n ? p : 0;
+}
+
+/* zlib from bit `bit` of the payload in[0 .. n) to the end of the stream, text_made bytes of text in front of out (the last 32 KiB
+   of them are the dictionary); true: the final block ended, *end_byte is the byte behind it and *made the bytes written */
+static bool inflate_rest_on_host(const unsigned char* in, size_t n, uint64_t bit, char* text, uint64_t text_made, uint64_t cap, size_t* end_byte,
+                                 uint64_t* made) {
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    if (inflateInit2(&zs, -15) != Z_OK) return false;
+    size_t at = (size_t)(bit >> 3);
+    bool ok = at < n;
+    if (ok && (bit & 7)) {
+        ok = inflatePrime(&zs, 8 - (int)(bit & 7), in[at] >> (bit & 7)) == Z_OK;
+        at++;
+    }
+    const uint64_t dl = std::min<uint64_t>(text_made, 32768);
+    if (ok && dl) ok = inflateSetDictionary(&zs, (const Bytef*)(text + text_made - dl), (uInt)dl) == Z_OK;
+    uint64_t done = 0;
+    int rc = Z_OK;
+    while (ok && rc != Z_STREAM_END) {
+        if (zs.avail_in == 0) {
+            zs.next_in = (Bytef*)(in + at);
+            zs.avail_in = (uInt)std::min<size_t>(n - at, 1u << 30);
+            at += zs.avail_in;
+        }
+        zs.next_out = (Bytef*)(text + text_made + done);
+        const uInt room = (uInt)std::min<uint64_t>(cap - done, 1u << 30);
+        zs.avail_out = room;
+        const uInt fed = zs.avail_in;
+        rc = inflate(&zs, Z_NO_FLUSH);
+        done += room - zs.avail_out;
+        if (rc != Z_OK && rc != Z_STREAM_END) ok = false;
+        else if (rc == Z_OK && fed == zs.avail_in && room == zs.avail_out && (fed == 0 || room == 0)) ok = false; /* out of input or of room */
+    }
+    if (ok) {
+        *end_byte = at - zs.avail_in;
+        *made = done;
+    }
+    inflateEnd(&zs);
+    return ok;
+}
+
+/* The member at in[0 .. fsize) through the hook into text[0 .. want); true: `want` bytes whose CRC-32 and size are the trailer's,
+   *used the byte behind the trailer. */
+static bool gunzip_member_on_device(const unsigned char* in, size_t fsize, char* text, uint64_t want, size_t* used) {
+    const size_t p0 = gzip_payload_start(in, fsize);
+    if (!p0) return false;
+    const unsigned char* pay = in + p0;
+    const size_t pn = fsize - p0;
+    uint64_t bit = 0, made = 0;
+    uLong crc = crc32(0L, Z_NULL, 0);
+    size_t end_byte = 0;
+    bool final_seen = false;
+    while (!final_seen) {
+        const size_t at = (size_t)(bit >> 3);
+        if (at >= pn) return false;
+        const size_t wlen = (size_t)std::min<uint64_t>(pn - at, g_gzip_window);
+        const uint64_t dl = std::min<uint64_t>(made, 32768);
+        fpl_gzip_window r;
+        memset(&r, 0, sizeof(r));
+        g_gzip_windows++;
+        const int rc = g_gzip_inflate(g_gzip_inflate_user, pay + at, wlen, bit & 7, dl ? (const uint8_t*)text + made - dl : nullptr, (uint32_t)dl,
+                                      (uint8_t*)text + made, want - made, 0, &r);
+        const bool taken = rc == 0 && r.status == FPL_GZIP_OK && r.out_bytes <= want - made && r.end_bit > (bit & 7) && r.end_bit <= 8 * (uint64_t)wlen &&
+                           (r.final_block || wlen == pn - at || (r.end_bit >> 3) * 16 >= wlen); /* (it got somewhere) */
+        if (!taken) {
+            g_gzip_refused++;
+            uint64_t rest = 0;
+            if (!inflate_rest_on_host(pay, pn, bit, text, made, want - made, &end_byte, &rest)) return false;
+            for (uint64_t k = 0; k < rest; k += 1u << 30)
+                crc = crc32(crc, (const Bytef*)text + made + k, (uInt)std::min<uint64_t>(rest - k, 1u << 30));
+            made += rest;
+            break;
+        }
+        crc = crc32_combine(crc, r.crc32, (z_off_t)r.out_bytes);
+        made += r.out_bytes;
+        bit = 8 * (uint64_t)at + r.end_bit;
+        if (r.final_block) {
+            final_seen = true;
+            end_byte = (size_t)((bit + 7) >> 3);
+        }
+    }
+    if (end_byte + 8 > pn || made != want) return false;
+    const unsigned char* t = pay + end_byte;
+    const uint32_t t_crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    const uint32_t t_size = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+    if (t_crc != (uint32_t)crc || t_size != (uint32_t)made) return false;
+    *used = p0 + end_byte + 8;
+    return true;
+}
+
 static char* gunzip_single_to_memory(const string& path, uint64_t max_bytes, uint64_t* size_out, uint64_t* reserved) {
     const int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) return nullptr;
@@ -440,7 +561,15 @@ static char* gunzip_single_to_memory(const string& path, uint64_t max_bytes, uin
             madvise(base, (size_t)span, MADV_HUGEPAGE); /* (one fault per 2 MiB instead of per 4 KiB as the text arrives) */
             size_t used = 0, made = 0;
             attempts++;
-            const int rc = gunzip_member_into(in, fsize, base, (size_t)want, &used, &made);
+            /* --device_inflate: the first guess through the hook; whatever it does not carry to a trailer that agrees is done again
+               below, as without it */
+            int rc = 0;
+            if (g_gzip_inflate && k == 0 && gunzip_member_on_device(in, fsize, base, want, &used)) {
+                rc = 1;
+                made = (size_t)want;
+            } else {
+                rc = gunzip_member_into(in, fsize, base, (size_t)want, &used, &made);
+            }
             if (rc == 1 && made > 0) {
                 /* a whole member.  Zero padding may follow (zlib ignores it: so does this); anything else is another member --
                    not for this lane */
@@ -1753,6 +1882,8 @@ char* fplh_gunzip_to_memory(const char* path, int threads, uint64_t max_bytes, u
     return fplh::gunzip_members_to_memory(path, threads, max_bytes, size_out, reserved);
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
+void fplh_set_gzip_inflater(fplh::GzipInflateFn fn, void* user, uint64_t window_bytes) { fplh::set_gzip_inflater(fn, user, window_bytes); }
+void fplh_gzip_inflater_counts(uint64_t* windows, uint64_t* refused) { fplh::gzip_inflater_counts(windows, refused); }
 void fplh_gunzip_release(char* base, uint64_t reserved) {
     if (base) munmap(base, (size_t)reserved);
 }

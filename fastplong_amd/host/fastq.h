@@ -224,6 +224,19 @@ class ChunkedReader {
     double t_redo_ = 0;
 };
 
+/* --device_inflate for a one-member .gz: the single-member lane of gunzip_members_to_memory hands the member's deflate payload
+ * to `fn` (fpl_inflate_gzip, or a test's stand-in) window by window -- window_bytes of compressed data from the byte of the bit
+ * where the window before ended, the last 32 KiB of text as the dictionary, the text straight into the lane's destination.  THE
+ * HOST STAYS THE JUDGE: the member's CRC-32 and size are checked here, from the windows' CRCs folded with crc32_combine.  A window
+ * that is refused, a call that fails or a window that hardly advances: zlib inflates from that window's start bit to the member's
+ * end (inflatePrime + inflateSetDictionary).  A trailer that does not agree: the whole member goes through the host lane, as
+ * without the hook.  fn == nullptr takes the hook out.  window_bytes 0: 32 MiB. */
+typedef int (*GzipInflateFn)(void* user, const uint8_t* comp, uint64_t comp_bytes, uint64_t start_bit, const uint8_t* dict, uint32_t dict_len,
+                             uint8_t* out, uint64_t out_cap, uint32_t chunk_bytes, fpl_gzip_window* res);
+void set_gzip_inflater(GzipInflateFn fn, void* user, uint64_t window_bytes = 0);
+/* windows handed to the hook since the last call (0: the hook was not used), and how many of them the host inflated */
+void gzip_inflater_counts(uint64_t* windows, uint64_t* refused);
+
 /* multi-member gzip -> the inflated text in anonymous memory (fastq.cpp); nullptr when that does not apply */
 char* gunzip_members_to_memory(const std::string& path, int threads, uint64_t max_bytes, uint64_t* size_out, uint64_t* reserved);
 
@@ -270,6 +283,9 @@ uint64_t fplh_gz_members(void);       /* gzip members inflated on the worker poo
 char* fplh_gunzip_to_memory(const char* path, int threads, uint64_t max_bytes, uint64_t* size_out, uint64_t* reserved);
 void fplh_gunzip_release(char* base, uint64_t reserved);
 int fplh_have_libdeflate(void);
+/* test hooks: the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */
+void fplh_set_gzip_inflater(fplh::GzipInflateFn fn, void* user, uint64_t window_bytes);
+void fplh_gzip_inflater_counts(uint64_t* windows, uint64_t* refused);
 uint32_t fplh_batch_n(void* b);
 uint64_t fplh_batch_bytes(void* b);
 const uint8_t* fplh_batch_seq(void* b);

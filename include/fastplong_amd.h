@@ -479,6 +479,42 @@ int fpl_inflate_bgzf(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes
                      uint64_t out_bytes);
 void fpl_inflater_destroy(fpl_inflater* inf);
 
+/*
+ * ONE LONG deflate stream -- the payload of an ordinary one-member .gz -- inflated on the device, a window of compressed bytes per
+ * call (csrc/gzip_inflate.h).  FPL_ABI_VERSION stays 10: found by symbol lookup like fpl_inflate_bgzf, on the same handle.
+ *
+ *   fpl_inflate_gzip   comp[0 .. comp_bytes) is a stretch of the member's raw deflate payload (at most 128 MiB behind the start
+ *                      bit's byte) and start_bit the bit offset in it of a BLOCK START the caller knows: bit 0 of the payload, or
+ *                      where the call before ended.  dict[0 .. dict_len) are the bytes in front of that point, the last 32 KiB of
+ *                      them or all there are (dict_len <= 32768; NULL / 0 at a member's start).  The payload is cut into chunks of
+ *                      chunk_bytes (0: the default, 32 KiB; 64 .. 16 MiB), block starts inside them are guessed, every chunk is
+ *                      decoded on a wave of its own and the guesses are then checked along the chain; only what the chain proves
+ *                      is given out.  out[0 .. res->out_bytes) gets the bytes, at most out_cap of them.  One upload, the launches,
+ *                      one download; synchronous; bad arguments are FPL_ERR_ARG before anything runs.  One call at a time per handle.
+ *   res                status FPL_GZIP_OK: out_bytes bytes are what inflating from start_bit gives, crc32 is their CRC-32, end_bit
+ *                      is the bit offset in comp behind the last block decoded -- a block start for the next call, whose comp may
+ *                      begin at byte end_bit / 8 -- and final_block says that block was the stream's last.  A call may end before
+ *                      the end of comp (a block that goes on behind comp_bytes, a guess that was wrong, out_cap reached): the next
+ *                      call goes on from end_bit.  Any other status: REFUSED -- nothing of out is defined and the caller inflates
+ *                      from start_bit itself; the device never has the last word on a damaged stream.
+ */
+typedef struct fpl_gzip_window { /* 32 bytes */
+    uint64_t out_bytes;
+    uint64_t end_bit;
+    uint32_t status;
+    uint32_t crc32;
+    uint32_t final_block;
+    uint32_t chunks; /* chunks of the chain that were taken (for the curious) */
+} fpl_gzip_window;
+enum {
+    FPL_GZIP_OK = 0,
+    FPL_GZIP_MALFORMED = 1, /* not a deflate stream this decoder takes, from the very first block on */
+    FPL_GZIP_ROOM = 2,      /* the first block alone makes more bytes than out_cap or than the device's room for a chunk */
+    FPL_GZIP_OVERRUN = 3    /* the first block goes on behind comp_bytes */
+};
+int fpl_inflate_gzip(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes, uint64_t start_bit, const uint8_t* dict, uint32_t dict_len,
+                     uint8_t* out, uint64_t out_cap, uint32_t chunk_bytes, fpl_gzip_window* res);
+
 /* Page-locked host memory for the arrays handed to fpl_process_batch[_async] / fpl_process_text_async: the DMA engines read it
  * directly.  Blocks of 8 MB and more are anonymous memory on transparent huge pages, touched and registered with the runtime
  * (hipHostRegister, portable across devices) -- locking 4 KB pages goes at 4 GB/s, 370 huge pages take 13 ms for 740 MB; smaller

@@ -289,6 +289,9 @@ fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
 int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
     return n_blocks ? FPL_ERR_NO_DEVICE : FPL_OK;
 }
+int fpl_inflate_gzip(fpl_inflater*, const uint8_t*, uint64_t, uint64_t, const uint8_t*, uint32_t, uint8_t*, uint64_t, uint32_t, fpl_gzip_window*) {
+    return FPL_ERR_NO_DEVICE;
+}
 void fpl_inflater_destroy(fpl_inflater*) {}
 int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return FPL_ERR_ARG;
