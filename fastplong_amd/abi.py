@@ -169,6 +169,11 @@ FPL_BGZF_SIZE = 2
 FPL_BGZF_CRC = 3
 FPL_BGZF_OVERRUN = 4
 
+# struct fpl_emit_info (32 bytes, device memory): what fpl_emit_batch_device says about the batch it made
+EMIT_INFO_DTYPE = [("n_bytes", "<u8"), ("n_out", "<u4"), ("max_len", "<u4"), ("status", "<u4"), ("reserved", "<u4", (3,))]
+FPL_EMIT_BAD_WINDOW = 1  # status bit 0: a fragment window reaches outside its read
+FPL_EMIT_NO_ROOM = 2     # status bit 1: out_cap_bytes or out_cap_reads too small
+
 # ---- flat int64 counter layout (see the header) -------------------------------------------
 FPL_CYC_STRIDE = 32
 FPL_STATS_TAIL = 128 * 3 + 1024 + 2

@@ -25,6 +25,7 @@
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
 #include "gzip_inflate.h"
+#include "emit.h"
 
 using namespace fpl;
 
@@ -64,6 +65,10 @@ struct fpl_ctx {
     DevBuf<u8> d_stats_flags;
     DevBuf<u64> d_extra_scratch; /* the post-only pass's own slabs / flags (it runs on s_aux beside the reduce of k_stats_sorted) */
     DevBuf<u8> d_extra_flags;
+    /* fpl_emit_batch_device (csrc/emit.h): the layout's per-block sums, and per output read where its bytes come from */
+    DevBuf<u32> d_emit_cnt, d_emit_max;
+    DevBuf<u64> d_emit_bytes;
+    DevBuf<EmitFrom> d_emit_from;
     /* The end trims of batch k + 1 beside the kernels of batch k ("trim ahead"): the trim kernel is the first of a batch, needs
        nothing of the batch before, and is bound by memory latency where k_scan / k_stats_sorted are bound by instruction issue
        -- 0.5 ms of a 12.5 ms step when two whole batches run side by side (round 4, tools/overlap_probe.py).  It writes
@@ -804,6 +809,53 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
         ctx->batch_no++;
     }
     if (timing) ctx->ev_calls++;
+    return FPL_OK;
+}
+
+/* the layout's block sums grow together; the list of sources on its own (it follows the capacity the caller gives) */
+static int ensure_emit(fpl_ctx* ctx, u32 nblk, size_t n_from) {
+    if (!ctx->d_emit_cnt.holds(nblk)) {
+        const size_t cap = grown(nblk, 64);
+        FPL_HIP(regrow(ctx->d_emit_cnt.want(cap), ctx->d_emit_max.want(cap), ctx->d_emit_bytes.want(cap)));
+    }
+    FPL_HIP(ctx->d_emit_from.grow(n_from, 1024));
+    return FPL_OK;
+}
+
+int fpl_emit_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint32_t n_reads,
+                          const fpl_read_result* d_results, uint8_t* d_seq_out, uint8_t* d_qual_out, uint64_t out_cap_bytes,
+                          uint64_t* d_off_out, uint32_t out_cap_reads, uint32_t* d_src, uint8_t* d_kind, fpl_emit_info* d_info,
+                          void* stream_v) {
+    if (!ctx || !d_info) return FPL_ERR_ARG;
+    if (n_reads && (!d_seq || !d_qual || !d_off || !d_results || !d_seq_out || !d_qual_out || !d_off_out)) return FPL_ERR_ARG;
+    if (n_reads > (1u << 30)) return FPL_ERR_ARG;
+    if (ctx->hcfg.defer) {
+        ctx->err = "fpl_emit_batch_device: with break_enabled / mask_enabled the output reads are the fragment list's (fpl_get_fragments)";
+        return FPL_ERR_STATE;
+    }
+    hipStream_t stream = (hipStream_t)stream_v;
+    FPL_HIP(hipSetDevice(ctx->device));
+    if (!n_reads) {
+        FPL_HIP(hipMemsetAsync(d_info, 0, sizeof(fpl_emit_info), stream));
+        if (d_off_out) FPL_HIP(hipMemsetAsync(d_off_out, 0, sizeof(uint64_t), stream));
+        return FPL_OK;
+    }
+    const u32 nblk = cdiv(n_reads, (u32)EM_LAYOUT_READS);
+    /* (the fill runs only when the output reads fit the caller's capacity, and a read gives two at the most) */
+    const size_t n_from = (size_t)std::min<uint64_t>(2ull * n_reads, out_cap_reads);
+    const int r = ensure_emit(ctx, nblk, n_from ? n_from : 1);
+    if (r != FPL_OK) return r;
+    hipLaunchKernelGGL(k_emit_count, dim3(nblk), dim3(EM_LAYOUT_READS), 0, stream, d_off, d_results, n_reads, ctx->d_emit_cnt.ptr,
+                       ctx->d_emit_bytes.ptr, ctx->d_emit_max.ptr);
+    hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(EM_SCAN_BLOCKS), 0, stream, ctx->d_emit_cnt.ptr, ctx->d_emit_bytes.ptr,
+                       (const u32*)ctx->d_emit_max.ptr, nblk, (u64)out_cap_bytes, out_cap_reads, d_off_out, d_info);
+    hipLaunchKernelGGL(k_emit_fill, dim3(nblk), dim3(EM_LAYOUT_READS), 0, stream, d_off, d_results, n_reads, (const u32*)ctx->d_emit_cnt.ptr,
+                       (const u64*)ctx->d_emit_bytes.ptr, (const fpl_emit_info*)d_info, d_off_out, d_src, d_kind, ctx->d_emit_from.ptr);
+    /* the output's size is known on the device only: a grid for the most the capacity admits, whose waves walk the tiles there are */
+    hipLaunchKernelGGL(k_emit_gather, dim3(emit_gather_blocks(out_cap_bytes, ctx->n_cu)), dim3(EM_GATHER_THREADS), 0, stream,
+                       (const u8*)d_seq, (const u8*)d_qual, (const uint64_t*)d_off_out, (const EmitFrom*)ctx->d_emit_from.ptr,
+                       (const fpl_emit_info*)d_info, d_seq_out, d_qual_out);
+    FPL_HIP(hipGetLastError());
     return FPL_OK;
 }
 

@@ -27,6 +27,7 @@ EXPORTS = [
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
+    "fpl_emit_batch_device",
 ]
 
 
@@ -162,6 +163,10 @@ def load_library(path=None):
         L.fpl_inflate_gzip.restype = C.c_int
         L.fpl_inflate_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                        C.c_uint32, C.c_void_p]
+    if hasattr(L, "fpl_emit_batch_device"):  # (found by name as well: without it Engine.emit_device raises)
+        L.fpl_emit_batch_device.restype = C.c_int
+        L.fpl_emit_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -453,6 +458,54 @@ class Engine:
                                                     seq_t.numel(), int(max_read_len), results_t.data_ptr(),
                                                     C.c_void_p(stream)), "fpl_process_batch_device")
         return results_t
+
+    def emit_device(self, seq_t, qual_t, off_t, results_t, stream=None, seq_out=None, qual_out=None, off_out=None, src=None, kind=None):
+        """fpl_emit_batch_device: the passing, trimmed reads of a batch (the tensors given to process_device and the records it
+        wrote) as a CSR batch on the device -> (seq_out, qual_out, off_out, src, kind, info_t).  Tensors that are not given are
+        made at the sizes that always suffice (seq_t.numel() bytes, 2 n reads); given ones set the capacities: seq_out and
+        qual_out (uint8, equally long), off_out (int64, reads + 1), src (int32) and kind (uint8) with a slot per read off_out
+        has room for.  Asynchronous on `stream` (default: torch's current stream) and without a synchronize: the tensors hold
+        the batch once the stream has got there, info_t (32 bytes, uint8; emit_info reads it back) says how much of them it
+        fills.  Behind a process_device on the same stream the two calls need nothing between them."""
+        import torch
+
+        if not hasattr(self.L, "fpl_emit_batch_device"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_emit_batch_device")
+        dev = seq_t.device
+        n = max(off_t.numel() - 1, 0)
+        if seq_out is None:
+            seq_out = torch.empty(max(seq_t.numel(), 1), dtype=torch.uint8, device=dev)
+        if qual_out is None:
+            qual_out = torch.empty(seq_out.numel(), dtype=torch.uint8, device=dev)
+        if off_out is None:
+            off_out = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)
+        cap_reads = off_out.numel() - 1
+        if src is None:
+            src = torch.empty(max(cap_reads, 1), dtype=torch.int32, device=dev)
+        if kind is None:
+            kind = torch.empty(max(cap_reads, 1), dtype=torch.uint8, device=dev)
+        if qual_out.numel() != seq_out.numel() or cap_reads < 0 or src.numel() < cap_reads or kind.numel() < cap_reads:
+            raise FplError("emit_device: seq_out / qual_out differ in length, or src / kind are shorter than off_out admits")
+        for t, dt in ((seq_out, torch.uint8), (qual_out, torch.uint8), (off_out, torch.int64), (src, torch.int32), (kind, torch.uint8)):
+            if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise FplError("emit_device: the outputs are contiguous tensors on the batch's device (uint8, uint8, int64, int32, uint8)")
+        info_t = torch.empty(32 + 16, dtype=torch.uint8, device=dev)
+        spare = info_t[32:].data_ptr()  # (an empty tensor has no address; a capacity of zero bytes is legal and needs one)
+        info_t = info_t[:32]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self.L.fpl_emit_batch_device(self.h, seq_t.data_ptr(), qual_t.data_ptr(), off_t.data_ptr(), n, results_t.data_ptr(),
+                                                 seq_out.data_ptr() or spare, qual_out.data_ptr() or spare, seq_out.numel(),
+                                                 off_out.data_ptr(), cap_reads, src.data_ptr() or None, kind.data_ptr() or None,
+                                                 info_t.data_ptr(), C.c_void_p(stream)),
+                    "fpl_emit_batch_device")
+        return seq_out, qual_out, off_out, src, kind, info_t
+
+    @staticmethod
+    def emit_info(info_t):
+        """the 32 bytes of emit_device's info_t, read back (this waits for the stream) -> dict(n_bytes, n_out, max_len, status)"""
+        r = info_t.cpu().numpy().view(abi.EMIT_INFO_DTYPE)[0]
+        return dict(n_bytes=int(r["n_bytes"]), n_out=int(r["n_out"]), max_len=int(r["max_len"]), status=int(r["status"]))
 
     @staticmethod
     def results_to_numpy(results_t, n):

@@ -515,6 +515,47 @@ enum {
 int fpl_inflate_gzip(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes, uint64_t start_bit, const uint8_t* dict, uint32_t dict_len,
                      uint8_t* out, uint64_t out_cap, uint32_t chunk_bytes, fpl_gzip_window* res);
 
+/*
+ * The passing, trimmed reads of a resident batch as a CSR batch in device memory (csrc/emit.h): what a writer makes of the
+ * records of fpl_process_batch_device, made where the bases are, so that a second consumer on the device -- an aligner, a k-mer
+ * counter, another fpl_process_batch_device -- never meets the host.  FPL_ABI_VERSION stays 10: found by symbol lookup like the
+ * inflater's calls; a library without it is a valid v10 library.
+ *
+ *   d_seq, d_qual, d_off, n_reads   the batch as it was handed to fpl_process_batch_device; d_results its records.
+ *   The output read for input read i, fragment f is the window [d_off[i] + frag_start[f], + frag_len[f]) of d_seq and of d_qual.
+ *   A fragment is put out when the read is not dropped, f < n_frag and code[f] == FPL_PASS_FILTER; the output is in input order,
+ *   fragment 0 before fragment 1 -- the order, and the bases and quality lines, of what the host's formatter writes to --out.
+ *   d_seq_out, d_qual_out   out_cap_bytes bytes each; output read j occupies [d_off_out[j], d_off_out[j + 1]) of both.  No alignment
+ *                           is asked of them; they must not overlap the inputs.
+ *   d_off_out               room for out_cap_reads + 1 offsets; d_off_out[0] = 0.
+ *   d_src, d_kind           per output read the index of its input read and the record's kind (0 unsplit, 1 / 2 the left / right
+ *                           part of a middle-adapter split): what a host needs to attach the names.  Either may be NULL.
+ *   d_info                  32 bytes in DEVICE memory: the only thing a consumer reads back before it can size its next call.
+ * out_cap_bytes = d_off[n_reads] and out_cap_reads = 2 * n_reads ALWAYS suffice: the fragments of a read are disjoint windows of it.
+ *
+ * The records are the caller's memory and are not trusted: a counted window that reaches outside its read sets status bit 0,
+ * totals beyond out_cap_bytes / out_cap_reads set bit 1.  With any bit set n_out = 0, n_bytes = 0, d_off_out[0] = 0 and NOTHING
+ * else is written; no read ever leaves [d_off[i], d_off[i + 1]) and no write the capacities.  (d_off itself is the caller's promise,
+ * as for fpl_process_batch_device: non-decreasing.)
+ *
+ * Asynchronous on `stream` and without a wait on the host (the context's workspace -- the layout's per-block sums and eight bytes
+ * per output read -- grows like every other: rarely, with headroom, behind a device-wide wait).  Placed on the stream behind the
+ * fpl_process_batch_device that writes d_results, it is ordered behind it.  n_reads == 0 gives an all-zero info.
+ * FPL_ERR_ARG: ctx or d_info NULL, n_reads > 0 with any other pointer but d_src / d_kind NULL, n_reads > 2^30.  FPL_ERR_STATE:
+ * a context with break_enabled / mask_enabled -- its reads live in the fragment list (fpl_get_fragments), not in the records.
+ */
+typedef struct fpl_emit_info { /* 32 bytes, written in DEVICE memory */
+    uint64_t n_bytes;          /* bytes of d_seq_out / d_qual_out used = d_off_out[n_out] */
+    uint32_t n_out;            /* output reads */
+    uint32_t max_len;          /* longest output read */
+    uint32_t status;           /* 0 ok; bit 0: a fragment window reaches outside its read; bit 1: out_cap_bytes or out_cap_reads too small */
+    uint32_t reserved[3];
+} fpl_emit_info;
+int fpl_emit_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint32_t n_reads,
+                          const fpl_read_result* d_results, uint8_t* d_seq_out, uint8_t* d_qual_out, uint64_t out_cap_bytes,
+                          uint64_t* d_off_out, uint32_t out_cap_reads, uint32_t* d_src, uint8_t* d_kind, fpl_emit_info* d_info,
+                          void* stream);
+
 /* Page-locked host memory for the arrays handed to fpl_process_batch[_async] / fpl_process_text_async: the DMA engines read it
  * directly.  Blocks of 8 MB and more are anonymous memory on transparent huge pages, touched and registered with the runtime
  * (hipHostRegister, portable across devices) -- locking 4 KB pages goes at 4 GB/s, 370 huge pages take 13 ms for 740 MB; smaller

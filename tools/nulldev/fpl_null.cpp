@@ -293,6 +293,11 @@ int fpl_inflate_gzip(fpl_inflater*, const uint8_t*, uint64_t, uint64_t, const ui
     return FPL_ERR_NO_DEVICE;
 }
 void fpl_inflater_destroy(fpl_inflater*) {}
+/* (the emitted batch lives in device memory: the null device has none) */
+int fpl_emit_batch_device(fpl_ctx*, const uint8_t*, const uint8_t*, const uint64_t*, uint32_t, const fpl_read_result*, uint8_t*, uint8_t*, uint64_t,
+                          uint64_t*, uint32_t, uint32_t*, uint8_t*, fpl_emit_info*, void*) {
+    return FPL_ERR_NO_DEVICE;
+}
 int fpl_get_gzip_batches(const fpl_ctx* ctx, uint64_t* out) {
     if (!ctx || !out) return FPL_ERR_ARG;
     *out = 0;
