@@ -168,6 +168,17 @@ FPL_BGZF_MALFORMED = 1
 FPL_BGZF_SIZE = 2
 FPL_BGZF_CRC = 3
 FPL_BGZF_OVERRUN = 4
+# struct fpl_bam_window (64 bytes): the header of a BGZF batch (fpl_peek_bgzf_bam / fpl_wait_bgzf_bam); status: FPL_BAMW_*
+BAM_WINDOW_DTYPE = [("status", "<u4"), ("n_reads", "<u4"), ("n_bases", "<u8"), ("max_read_len", "<u4"), ("segments", "<u4"),
+                    ("name_bytes", "<u8"), ("records_seen", "<u8"), ("tail_bytes", "<u4"), ("rewalked", "<u4"), ("bad_index", "<u8"),
+                    ("bad_pos", "<u8")]
+FPL_BAMW_OK = 0
+FPL_BAMW_BLOCK = 1
+FPL_BAMW_RECORD = 2
+FPL_BAMW_TAIL_ROOM = 3
+FPL_BAMW_TOO_MANY = 4
+FPL_BAMW_CHAIN = 5
+FPL_BAM_TAIL_DEFAULT = 8 << 20
 
 # struct fpl_emit_info (32 bytes, device memory): what fpl_emit_batch_device says about the batch it made
 EMIT_INFO_DTYPE = [("n_bytes", "<u8"), ("n_out", "<u4"), ("max_len", "<u4"), ("status", "<u4"), ("reserved", "<u4", (3,))]

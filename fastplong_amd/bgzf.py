@@ -1,0 +1,87 @@
+"""A BAM file's bytes cut into what Engine.submit_bgzf takes: the BGZF blocks' descriptors, and where the first record starts.
+Pure Python; the structure checks are the reader's (host/bam.cpp): a block is a gzip member with the BC extra field."""
+import struct
+import zlib
+
+import numpy as np
+
+from . import abi
+
+
+class BgzfError(ValueError):
+    pass
+
+
+def block_len(data, pos):
+    """BSIZE + 1 of the block whose header starts at pos"""
+    if len(data) - pos < 18 or data[pos:pos + 3] != b"\x1f\x8b\x08" or not data[pos + 3] & 4:
+        raise BgzfError("no BGZF block at offset %d" % pos)
+    xlen = struct.unpack_from("<H", data, pos + 10)[0]
+    k = 0
+    while k + 4 <= xlen:
+        f = pos + 12 + k
+        slen = struct.unpack_from("<H", data, f + 2)[0]
+        if data[f:f + 2] == b"BC" and slen == 2:
+            n = struct.unpack_from("<H", data, f + 4)[0] + 1
+            if n < 12 + xlen + 8 or pos + n > len(data):
+                break
+            return n
+        k += 4 + slen
+    raise BgzfError("no BGZF block at offset %d" % pos)
+
+
+def blocks(data, begin=0, end=None):
+    """the blocks of data[begin:end) -> (descriptors as an array of abi.BGZF_BLOCK_DTYPE with comp_off relative to `begin` and
+    out_off counted from this stretch's first inflated byte, file offsets of the blocks).  Empty blocks (the EOF marker) make no
+    bytes and are left out.  Headers with a name, a comment or a header CRC (which BGZF does not allow) are refused here."""
+    end = len(data) if end is None else end
+    desc, offs, pos, out = [], [], begin, 0
+    while pos < end:
+        n = block_len(data, pos)
+        if data[pos + 3] & (2 | 8 | 16):
+            raise BgzfError("the block at offset %d has header fields BGZF does not allow" % pos)
+        hdr = 12 + struct.unpack_from("<H", data, pos + 10)[0]
+        crc, isize = struct.unpack_from("<II", data, pos + n - 8)
+        if isize > 65536:
+            raise BgzfError("the block at offset %d has a bad size" % pos)
+        if isize:
+            desc.append((pos + hdr - begin, out, n - hdr - 8, isize, crc, 1))
+            offs.append(pos)
+            out += isize
+        pos += n
+    return np.array(desc, dtype=np.dtype(abi.BGZF_BLOCK_DTYPE)), offs
+
+
+def inflate_block(data, pos):
+    """the bytes of the block at pos, by zlib (the trailer is NOT checked: the recovery path of a caller that judges it itself)"""
+    n = block_len(data, pos)
+    hdr = 12 + struct.unpack_from("<H", data, pos + 10)[0]
+    return zlib.decompressobj(-15).decompress(data[pos + hdr:pos + n - 8])
+
+
+def header_len(data):
+    """bytes of the inflated stream in front of the first record: magic, l_text, text, n_ref and the references.  Inflates as many
+    leading blocks as the header needs."""
+    raw, pos = b"", 0
+
+    def need(n):
+        nonlocal raw, pos
+        while len(raw) < n:
+            if pos >= len(data):
+                raise BgzfError("the file ends inside the BAM header")
+            raw += inflate_block(data, pos)
+            pos += block_len(data, pos)
+
+    need(12)
+    if raw[:4] != b"BAM\1":
+        raise BgzfError("the inflated stream does not start with BAM\\1")
+    p = 8 + struct.unpack_from("<I", raw, 4)[0]
+    need(p + 4)
+    n_ref = struct.unpack_from("<I", raw, p)[0]
+    p += 4
+    for _ in range(n_ref):
+        need(p + 4)
+        p += 4 + struct.unpack_from("<I", raw, p)[0]
+        need(p + 4)
+        p += 4
+    return p

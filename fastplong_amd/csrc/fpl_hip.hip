@@ -24,14 +24,18 @@
 #include "gz_emit.h"
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
+#include "bam_walk.h"
 #include "gzip_inflate.h"
 #include "emit.h"
 
 using namespace fpl;
 
 /* what a slot holds: a CSR batch (fpl_process_batch_async), a FASTQ text chunk (fpl_process_text_async) or BAM records
-   (fpl_process_bam_async).  fpl_wait / fpl_wait_bam_gz collect CSR and BAM batches, fpl_wait_text* text batches. */
-enum class BatchKind { CSR, Text, BAM };
+   (fpl_process_bam_async), or a BAM's BGZF blocks whose records the device finds itself (fpl_process_bgzf_bam_async).  fpl_wait /
+   fpl_wait_bam_gz collect CSR and BAM batches, fpl_wait_text* text batches, fpl_wait_bgzf_bam BGZF batches. */
+enum class BatchKind { CSR, Text, BAM, BGZF };
+/* the slot holds BAM records on the device: d_bam, d_rec and the decoded arrays (what the BAM forms of the gzip kernels read) */
+static inline bool bam_records(BatchKind k) { return k == BatchKind::BAM || k == BatchKind::BGZF; }
 
 struct fpl_ctx {
     int device = -1;
@@ -141,6 +145,23 @@ struct fpl_ctx {
             uint8_t *seq_out = nullptr, *qual_out = nullptr;
             DevBuf<u8> d_bam;
             DevBuf<uint64_t> d_rec;
+            /* a BGZF batch (csrc/bam_walk.h): d_bam is [room for the tail | the inflated bytes], the walk fills d_rec and d_off.
+               Stage 1 (upload, inflate, walk, the header's way back) is enqueued at submission, stage 2 (decode, the per-read
+               kernels, the way back of records and names) once the header is in -- by fpl_start_bgzf_bam or by the wait */
+            int stage = 0;
+            DevBuf<u8> d_comp;
+            DevBuf<fpl_bgzf_block> d_blocks;
+            DevBuf<u32> d_next;
+            DevBuf<u64> d_cand;
+            DevBuf<BamSeg> d_segs;
+            DevBuf<u32> d_lists;
+            DevBuf<BamSegBase> d_bases;
+            DevBuf<fpl_bam_window> d_whdr;
+            PinBuf<fpl_bam_window> h_whdr;
+            DevBuf<u8> d_names;
+            DevBuf<uint64_t> d_name_off;
+            PinBuf<u8> h_names;
+            PinBuf<uint64_t> h_name_off;
         } bam;
     };
     Slot slot[FPL_MAX_IN_FLIGHT];
@@ -158,6 +179,12 @@ struct fpl_ctx {
     uint64_t forms[6] = {0, 0, 0, 0, 0, 0}; /* fpl_get_batch_forms */
     bool text_gzip = false;    /* fpl_set_text_gzip */
     bool bam_gzip = false;     /* fpl_set_bam_gzip */
+    /* fpl_process_bgzf_bam_async: the tail between two submissions and the walk's state live on the device (csrc/bam_walk.h) */
+    DevBuf<BamWalkState> d_bamw_state;
+    DevBuf<u8> d_bam_tail;
+    uint64_t bam_tail_cap = FPL_BAM_TAIL_DEFAULT;
+    bool bam_fresh = true;     /* the context holds no tail as far as the host knows (no submission since it last looked): skip is allowed */
+    u32 bam_seg_bytes = 0;     /* FPL_BAM_SEG_BYTES (read in fpl_create; 0: BAMW_DEFAULT_SEG) */
     uint64_t gz_batches = 0;   /* fpl_get_gzip_batches */
     std::string err;
 };
@@ -272,6 +299,10 @@ int fpl_create(fpl_ctx** out, const fpl_options* opt, const char* start_adapter,
         FPL_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
         FPL_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
         if (const char* e = getenv("FPL_NO_OVERLAP")) ctx->overlap = atoi(e) == 0;
+        if (const char* e = getenv("FPL_BAM_SEG_BYTES")) { /* (a test hook: small segments; a value the walk cannot use is ignored) */
+            const long v = atol(e);
+            ctx->bam_seg_bytes = v >= (long)BAMW_MIN_SEG && v <= (1l << 30) ? (u32)v : 0;
+        }
         for (auto& sl : ctx->slot) {
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_h2d, hipEventDisableTiming));
             FPL_HIP(hipEventCreateWithFlags(&sl.ev_kern, hipEventDisableTiming));
@@ -906,7 +937,7 @@ static int ensure_text_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint64_t n_bytes) {
 /* behind the per-read kernels of the batch, on their stream: where every record's output and every deflate block starts */
 static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
     fpl_ctx::Slot::Gzip& g = sl.gzip;
-    const bool bam = sl.kind == BatchKind::BAM;
+    const bool bam = bam_records(sl.kind);
     if (!g.d_hdr.ptr) {
         FPL_HIP(g.d_hdr.alloc(1));
         FPL_HIP(g.h_hdr.alloc(1));
@@ -949,7 +980,7 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(g.d_tmp.grow(out_want + 16, 4096));
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
-    if (sl.kind == BatchKind::BAM)
+    if (bam_records(sl.kind))
         hipLaunchKernelGGL(k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
@@ -995,7 +1026,7 @@ static int submit_tail(fpl_ctx* ctx, fpl_ctx::Slot& sl, hipEvent_t inputs, u32 n
     ctx->next_inputs_event = nullptr;
     if (rd != FPL_OK) return rd;
     FPL_HIP(hipEventRecord(sl.ev_kern, ctx->stream));
-    if (sl.kind == BatchKind::BAM) {
+    if (bam_records(sl.kind)) {
         const fpl_ctx::Slot::Bam& b = sl.bam;
         FPL_HIP(hipStreamWaitEvent(ctx->s_d2h, sl.ev_parsed, 0));
         if (b.bases && b.seq_out) {
@@ -1221,7 +1252,7 @@ static int wait_batch(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx) return FPL_ERR_ARG;
     if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
     fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
-    if (sl.kind == BatchKind::Text) return FPL_ERR_STATE; /* (fpl_wait_text) */
+    if (sl.kind == BatchKind::Text || sl.kind == BatchKind::BGZF) return FPL_ERR_STATE; /* (fpl_wait_text, fpl_wait_bgzf_bam) */
     ctx->waited++;
     if (sl.rc != FPL_OK) return sl.rc; /* nothing was enqueued behind the failure */
     if (sl.n_reads == 0) return FPL_OK;
@@ -1413,6 +1444,295 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
     return FPL_OK;
 }
 
+/* ---- BGZF blocks in, records out: bgzf_inflate.h -> bam_walk.h -> bam_decode.h -> the per-read kernels ---- */
+static bool bgzf_in_flight(const fpl_ctx* ctx) {
+    for (u32 k = ctx->waited; k != ctx->submitted; k++)
+        if (ctx->slot[k % FPL_MAX_IN_FLIGHT].kind == BatchKind::BGZF) return true;
+    return false;
+}
+/* the walk's state and the tail buffer, made on first use (all zero: no tail, nothing refused) */
+/* k_bgzf_inflate's grid: a wave per block; as many workgroups as the device keeps resident (the tables' LDS bounds them), the rest
+   off the counter */
+static inline u32 bgzf_grid(u32 n_blocks, u32 n_cu) {
+    const u32 per_cu = std::max<u32>(1, std::min<u32>(8, (u32)(160u * 1024 / (sizeof(BgzfWaveLds) * (BGZF_THREADS / WAVE) + 1024))));
+    return std::min<u32>((n_blocks + BGZF_THREADS / WAVE - 1) / (BGZF_THREADS / WAVE), n_cu * per_cu);
+}
+/* room for a submission's names: a quarter of [tail room | inflated bytes] and 1 MiB, never more than all of it (a name is part of
+   its record).  Records whose names take more than that are FPL_BAMW_TOO_MANY, as more than a record per 64 bytes is. */
+static inline uint64_t bam_names_cap(uint64_t hi) { return std::min<uint64_t>(hi, hi / 4 + (1u << 20)); }
+static int ensure_bam_tail(fpl_ctx* ctx) {
+    if (!ctx->d_bamw_state.ptr) {
+        FPL_HIP(ctx->d_bamw_state.alloc(1));
+        FPL_HIP(hipMemset(ctx->d_bamw_state.ptr, 0, sizeof(BamWalkState)));
+    }
+    if (!ctx->d_bam_tail.ptr) FPL_HIP(ctx->d_bam_tail.alloc((size_t)std::max<uint64_t>(ctx->bam_tail_cap, 1)));
+    return FPL_OK;
+}
+
+int fpl_process_bgzf_bam_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_bytes, const fpl_bgzf_block* blocks, uint32_t n_blocks,
+                               uint64_t skip) {
+    if (!ctx || (n_blocks && !blocks) || (comp_bytes && !comp)) return FPL_ERR_ARG;
+    if (ctx->submitted - ctx->waited >= FPL_MAX_IN_FLIGHT) return FPL_ERR_STATE;
+    FPL_HIP(hipSetDevice(ctx->device));
+    if (ctx->hcfg.defer) return FPL_ERR_STATE; /* (--break / --mask read their fragment lists batch by batch: the CSR entry points) */
+    if (skip && !ctx->bam_fresh) {
+        ctx->err = "fpl_process_bgzf_bam_async: skip is valid only while the context holds no tail";
+        return FPL_ERR_ARG;
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_blocks; i++) { /* every range, before anything is enqueued; in order and without gaps */
+        const fpl_bgzf_block& d = blocks[i];
+        if (d.comp_len > BGZF_MAX_COMP || d.isize > BGZF_MAX_ISIZE || d.comp_off > comp_bytes || comp_bytes - d.comp_off < d.comp_len ||
+            d.out_off != total)
+            return FPL_ERR_ARG;
+        total += d.isize;
+        if (total > 0xFFFFFFF0ull) return FPL_ERR_ARG;
+    }
+    BamWalkJob j;
+    if (!bam_walk_plan(j, ctx->bam_tail_cap, total, skip, ctx->bam_seg_bytes)) return FPL_ERR_ARG;
+    fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
+    fpl_ctx::Slot::Bam& b = sl.bam;
+    sl.kind = BatchKind::BGZF;
+    sl.gz = ctx->bam_gzip;
+    sl.n_reads = 0;
+    sl.user_results = nullptr;
+    sl.rc = FPL_OK;
+    b.stage = 0;
+    b.o_begin = b.bases = 0;
+    b.seq_out = b.qual_out = nullptr;
+    int r = ensure_host_streams(ctx);
+    if (r != FPL_OK) return r;
+    r = ensure_bam_tail(ctx);
+    if (r != FPL_OK) return r;
+    const u32 rec_cap = bam_walk_rec_cap(total);
+    const uint64_t hi = j.tail_cap + total;
+    if (!b.d_whdr.ptr) {
+        FPL_HIP(b.d_whdr.alloc(1));
+        FPL_HIP(b.h_whdr.alloc(1));
+        FPL_HIP(b.d_next.alloc(1));
+    }
+    if (!b.d_bam.holds(hi + BAM_PAD)) FPL_HIP(regrow(b.d_bam.want(grown(hi, BAM_PAD))));
+    FPL_HIP(b.d_names.grow((size_t)bam_names_cap(hi) + 1, 4096));
+    if (!sl.d_results.holds(rec_cap)) {
+        const size_t cap = grown(rec_cap, 16);
+        FPL_HIP(regrow(sl.d_off.want(cap + 1), sl.d_results.want(cap)));
+    }
+    if (!b.d_name_off.holds((size_t)rec_cap + 1)) {
+        const size_t cap = grown(rec_cap, 16);
+        FPL_HIP(regrow(b.d_rec.want(cap + 1), b.d_name_off.want(cap + 1)));
+    }
+    FPL_HIP(b.d_rec.grow((size_t)rec_cap + 1, 16)); /* (a slot fpl_process_bam_async sized before) */
+    FPL_HIP(b.d_comp.grow((size_t)comp_bytes + 1, 4096));
+    FPL_HIP(b.d_blocks.grow((size_t)n_blocks + 1, 64));
+    if (!b.d_cand.holds(j.n_seg)) {
+        const size_t cap = grown(j.n_seg, 64);
+        FPL_HIP(regrow(b.d_cand.want(cap), b.d_segs.want(cap), b.d_bases.want(cap)));
+    }
+    FPL_HIP(b.d_lists.grow((size_t)j.n_seg * j.per_seg, 4096));
+    j.buf = b.d_bam.ptr;
+    j.rec_cap = rec_cap;
+    j.st = ctx->d_bamw_state.ptr;
+    j.tail_buf = ctx->d_bam_tail.ptr;
+    j.blocks = b.d_blocks.ptr;
+    j.n_blocks = n_blocks;
+    j.cand = b.d_cand.ptr;
+    j.segs = b.d_segs.ptr;
+    j.lists = b.d_lists.ptr;
+    j.bases = b.d_bases.ptr;
+    j.hdr = b.d_whdr.ptr;
+    j.rec_start = b.d_rec.ptr;
+    j.off = sl.d_off.ptr;
+    j.name_off = b.d_name_off.ptr;
+    j.names = b.d_names.ptr;
+    j.names_cap = bam_names_cap(hi);
+    auto enqueue = [&]() -> int {
+        /* the upload on the copy stream; inflate and walk on the parse stream behind it, and behind the walk of the submission
+           before -- that order carries the tail; only the header comes back */
+        if (comp_bytes) FPL_HIP(hipMemcpyAsync(b.d_comp.ptr, comp, comp_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        if (n_blocks) FPL_HIP(hipMemcpyAsync(b.d_blocks.ptr, blocks, sizeof(fpl_bgzf_block) * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->s_h2d));
+        FPL_HIP(hipEventRecord(sl.ev_h2d, ctx->s_h2d));
+        hipStream_t st = ctx->s_parse;
+        FPL_HIP(hipStreamWaitEvent(st, sl.ev_h2d, 0));
+        if (n_blocks) {
+            FPL_HIP(hipMemsetAsync(b.d_next.ptr, 0, sizeof(u32), st));
+            const u32 grid = bgzf_grid(n_blocks, ctx->n_cu);
+            hipLaunchKernelGGL(k_bgzf_inflate, dim3(grid), dim3(BGZF_THREADS), 0, st, (const u8*)b.d_comp.ptr, b.d_blocks.ptr, n_blocks,
+                               b.d_bam.ptr + j.tail_cap, b.d_next.ptr);
+        }
+        bam_walk_enqueue(j, st);
+        FPL_HIP(hipGetLastError());
+        FPL_HIP(hipMemcpyAsync(b.h_whdr.ptr, b.d_whdr.ptr, sizeof(fpl_bam_window), hipMemcpyDeviceToHost, st));
+        FPL_HIP(hipEventRecord(sl.ev_parsed, st));
+        return FPL_OK;
+    };
+    r = enqueue();
+    if (r != FPL_OK) {
+        drain(ctx);
+        return r;
+    }
+    b.stage = 1;
+    ctx->bam_fresh = false;
+    ctx->submitted++;
+    return FPL_OK;
+}
+
+/* stage 2 of a BGZF batch: the header is in -- the decode, the per-read kernels, the way back of the records and the names */
+static int bgzf_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint8_t* seq_out, uint8_t* qual_out) {
+    fpl_ctx::Slot::Bam& b = sl.bam;
+    if (sl.kind != BatchKind::BGZF || b.stage != 1) return FPL_OK;
+    b.stage = 2;
+    FPL_HIP(hipEventSynchronize(sl.ev_parsed));
+    const fpl_bam_window h = *b.h_whdr.ptr;
+    sl.n_reads = 0;
+    if (h.status != FPL_BAMW_OK || h.n_reads == 0) return FPL_OK; /* nothing to run: the wait reports */
+    const u32 n = h.n_reads;
+    b.o_begin = 0;
+    b.bases = h.n_bases;
+    b.seq_out = seq_out;
+    b.qual_out = qual_out;
+    int r = ensure_slot(ctx, sl, n, h.n_bases + 16); /* (the decode writes whole 16-byte words; d_off / d_results hold rec_cap already) */
+    if (r != FPL_OK) return r;
+    FPL_HIP(b.h_names.grow((size_t)h.name_bytes + 1, 4096));
+    FPL_HIP(b.h_name_off.grow((size_t)n + 1, 1024));
+    FPL_HIP(hipStreamWaitEvent(ctx->stream, sl.ev_parsed, 0));
+    bam_launch(b.d_bam.ptr, b.d_rec.ptr, sl.d_off.ptr, n, 0, h.n_bases, sl.d_seq.ptr, sl.d_qual.ptr, ctx->stream);
+    FPL_HIP(hipGetLastError());
+    FPL_HIP(hipEventRecord(sl.ev_parsed, ctx->stream)); /* (from here on: the bases are decoded, as for a BAM batch) */
+    FPL_HIP(hipMemcpyAsync(b.h_names.ptr, b.d_names.ptr, (size_t)h.name_bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+    FPL_HIP(hipMemcpyAsync(b.h_name_off.ptr, b.d_name_off.ptr, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->s_d2h));
+    r = submit_tail(ctx, sl, sl.ev_parsed, n, h.n_bases, h.max_read_len);
+    if (r == FPL_OK) sl.n_reads = n;
+    return r;
+}
+
+/* the oldest BGZF batch in flight that is not started: what fpl_peek_bgzf_bam / fpl_start_bgzf_bam act on */
+static fpl_ctx::Slot* bgzf_pending(fpl_ctx* ctx) {
+    for (u32 k = ctx->waited; k != ctx->submitted; k++) {
+        fpl_ctx::Slot& sl = ctx->slot[k % FPL_MAX_IN_FLIGHT];
+        if (sl.kind == BatchKind::BGZF && sl.bam.stage == 1) return &sl;
+    }
+    return nullptr;
+}
+
+int fpl_peek_bgzf_bam(fpl_ctx* ctx, fpl_bam_window* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    fpl_ctx::Slot* sl = bgzf_pending(ctx);
+    if (!sl) return FPL_ERR_STATE;
+    memset(out, 0, sizeof(*out));
+    if (sl->rc != FPL_OK) return sl->rc;
+    FPL_HIP(hipSetDevice(ctx->device));
+    FPL_HIP(hipEventSynchronize(sl->ev_parsed));
+    *out = *sl->bam.h_whdr.ptr;
+    return FPL_OK;
+}
+
+int fpl_start_bgzf_bam(fpl_ctx* ctx, uint8_t* seq_out, uint8_t* qual_out) {
+    if (!ctx || (!seq_out) != (!qual_out)) return FPL_ERR_ARG;
+    fpl_ctx::Slot* sl = bgzf_pending(ctx);
+    if (!sl) return FPL_ERR_STATE;
+    if (sl->rc != FPL_OK) return sl->rc;
+    FPL_HIP(hipSetDevice(ctx->device));
+    const int r = bgzf_continue(ctx, *sl, seq_out, qual_out);
+    if (r != FPL_OK) sl->rc = r;
+    return r;
+}
+
+int fpl_wait_bgzf_bam(fpl_ctx* ctx, fpl_bam_window* out, const fpl_read_result** results, const uint8_t** names, const uint64_t** name_off,
+                      const uint8_t** gz, uint64_t* gz_len) {
+    if (!ctx || !out || (!gz) != (!gz_len)) return FPL_ERR_ARG;
+    if (ctx->submitted == ctx->waited) return FPL_ERR_STATE;
+    fpl_ctx::Slot& sl = ctx->slot[ctx->waited % FPL_MAX_IN_FLIGHT];
+    if (sl.kind != BatchKind::BGZF) return FPL_ERR_STATE; /* (fpl_wait, fpl_wait_text) */
+    memset(out, 0, sizeof(*out));
+    if (results) *results = nullptr;
+    if (names) *names = nullptr;
+    if (name_off) *name_off = nullptr;
+    if (gz) {
+        *gz = nullptr;
+        *gz_len = 0;
+    }
+    FPL_HIP(hipSetDevice(ctx->device));
+    if (sl.rc == FPL_OK) {
+        const int r = bgzf_continue(ctx, sl, nullptr, nullptr); /* (no-op when fpl_start_bgzf_bam did it) */
+        if (r != FPL_OK) sl.rc = r;
+    }
+    ctx->waited++;
+    if (sl.rc != FPL_OK) return sl.rc;
+    *out = *sl.bam.h_whdr.ptr;
+    if (out->status != FPL_BAMW_OK || sl.n_reads == 0) return FPL_OK;
+    if (gz && sl.gz) {
+        const int r = gz_emit(ctx, sl, gz, gz_len);
+        if (r != FPL_OK) return r;
+    }
+    FPL_HIP(hipEventSynchronize(sl.ev_done));
+    if (results) *results = sl.h_results.ptr;
+    if (names) *names = sl.bam.h_names.ptr;
+    if (name_off) *name_off = sl.bam.h_name_off.ptr;
+    return FPL_OK;
+}
+
+/* (the recovery calls run with no BGZF batch in flight: every walk is done -- its header was waited for -- and the state is at rest) */
+int fpl_bam_tail_get(fpl_ctx* ctx, uint8_t* buf, uint64_t cap, uint64_t* len) {
+    if (!ctx || !len) return FPL_ERR_ARG;
+    *len = 0;
+    if (bgzf_in_flight(ctx)) return FPL_ERR_STATE;
+    if (!ctx->d_bamw_state.ptr) return FPL_OK;
+    FPL_HIP(hipSetDevice(ctx->device));
+    BamWalkState st;
+    FPL_HIP(hipMemcpy(&st, ctx->d_bamw_state.ptr, sizeof(st), hipMemcpyDeviceToHost));
+    const uint64_t n = std::min<uint64_t>(st.tail_len, ctx->bam_tail_cap);
+    *len = n;
+    if (n > cap || (n && !buf)) return FPL_ERR_ARG;
+    if (n) FPL_HIP(hipMemcpy(buf, ctx->d_bam_tail.ptr, (size_t)n, hipMemcpyDeviceToHost));
+    return FPL_OK;
+}
+static int bam_state_update(fpl_ctx* ctx, bool set_tail, uint64_t tail_len) {
+    const int r = ensure_bam_tail(ctx);
+    if (r != FPL_OK) return r;
+    BamWalkState st;
+    FPL_HIP(hipMemcpy(&st, ctx->d_bamw_state.ptr, sizeof(st), hipMemcpyDeviceToHost));
+    st.refused = 0;
+    if (set_tail) {
+        st.tail_len = (u32)tail_len;
+        if (tail_len == 0) st.rec_base = 0;
+    }
+    FPL_HIP(hipMemcpy(ctx->d_bamw_state.ptr, &st, sizeof(st), hipMemcpyHostToDevice));
+    ctx->bam_fresh = st.tail_len == 0; /* (a refused first stretch left none: it is submitted again with its skip) */
+    return FPL_OK;
+}
+int fpl_bam_tail_set(fpl_ctx* ctx, const uint8_t* bytes, uint64_t len) {
+    if (!ctx || (len && !bytes) || len > ctx->bam_tail_cap) return FPL_ERR_ARG;
+    if (bgzf_in_flight(ctx)) return FPL_ERR_STATE;
+    FPL_HIP(hipSetDevice(ctx->device));
+    const int r = bam_state_update(ctx, true, len);
+    if (r != FPL_OK) return r;
+    if (len) FPL_HIP(hipMemcpy(ctx->d_bam_tail.ptr, bytes, (size_t)len, hipMemcpyHostToDevice));
+    return FPL_OK;
+}
+int fpl_resume_bgzf_bam(fpl_ctx* ctx) {
+    if (!ctx) return FPL_ERR_ARG;
+    if (bgzf_in_flight(ctx)) return FPL_ERR_STATE;
+    FPL_HIP(hipSetDevice(ctx->device));
+    return bam_state_update(ctx, false, 0);
+}
+int fpl_reserve_bam_tail(fpl_ctx* ctx, uint64_t bytes) {
+    if (!ctx || bytes > (1ull << 30)) return FPL_ERR_ARG;
+    if (bgzf_in_flight(ctx)) return FPL_ERR_STATE;
+    if (!ctx->d_bam_tail.ptr) { /* before the first use: exactly what was asked for */
+        ctx->bam_tail_cap = bytes;
+        return FPL_OK;
+    }
+    if (bytes <= ctx->bam_tail_cap) return FPL_OK;
+    FPL_HIP(hipSetDevice(ctx->device));
+    FPL_HIP(hipDeviceSynchronize());
+    DevBuf<u8> nw;
+    FPL_HIP(nw.alloc((size_t)bytes));
+    if (ctx->bam_tail_cap) FPL_HIP(hipMemcpy(nw.ptr, ctx->d_bam_tail.ptr, (size_t)ctx->bam_tail_cap, hipMemcpyDeviceToDevice));
+    ctx->d_bam_tail.swap(nw); /* (the old block goes with nw) */
+    ctx->bam_tail_cap = bytes;
+    return FPL_OK;
+}
+
 /* ---- BGZF inflate (bgzf_inflate.h): a handle of its own, no context ---- */
 struct fpl_inflater {
     int device = -1;
@@ -1485,9 +1805,7 @@ int fpl_inflate_bgzf(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes
     if (comp_bytes) FPL_HIP_RC(hipMemcpyAsync(inf->d_comp.ptr, comp, comp_bytes, hipMemcpyHostToDevice, s));
     FPL_HIP_RC(hipMemcpyAsync(inf->d_blocks.ptr, blocks, sizeof(fpl_bgzf_block) * (size_t)n_blocks, hipMemcpyHostToDevice, s));
     FPL_HIP_RC(hipMemsetAsync(inf->d_next.ptr, 0, sizeof(u32), s));
-    /* a wave per block; as many workgroups as the device keeps resident (the tables' LDS bounds them), the rest off the counter */
-    const u32 per_cu = std::max<u32>(1, std::min<u32>(8, (u32)(160u * 1024 / (sizeof(BgzfWaveLds) * (BGZF_THREADS / WAVE) + 1024))));
-    const u32 grid = std::min<u32>((n_blocks + BGZF_THREADS / WAVE - 1) / (BGZF_THREADS / WAVE), (u32)inf->n_cu * per_cu);
+    const u32 grid = bgzf_grid(n_blocks, (u32)inf->n_cu);
     hipLaunchKernelGGL(k_bgzf_inflate, dim3(grid), dim3(BGZF_THREADS), 0, s, (const u8*)inf->d_comp.ptr, inf->d_blocks.ptr, n_blocks, inf->d_out.ptr,
                        inf->d_next.ptr);
     FPL_HIP_RC(hipGetLastError());

@@ -28,6 +28,8 @@ EXPORTS = [
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
+    "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
+    "fpl_resume_bgzf_bam", "fpl_reserve_bam_tail",
 ]
 
 
@@ -167,6 +169,24 @@ def load_library(path=None):
         L.fpl_emit_batch_device.restype = C.c_int
         L.fpl_emit_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "fpl_process_bgzf_bam_async"):  # (found by name too: without them Engine.submit_bgzf raises)
+        L.fpl_process_bgzf_bam_async.restype = C.c_int
+        L.fpl_process_bgzf_bam_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64]
+        L.fpl_peek_bgzf_bam.restype = C.c_int
+        L.fpl_peek_bgzf_bam.argtypes = [C.c_void_p, C.c_void_p]
+        L.fpl_start_bgzf_bam.restype = C.c_int
+        L.fpl_start_bgzf_bam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fpl_wait_bgzf_bam.restype = C.c_int
+        L.fpl_wait_bgzf_bam.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.fpl_bam_tail_get.restype = C.c_int
+        L.fpl_bam_tail_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fpl_bam_tail_set.restype = C.c_int
+        L.fpl_bam_tail_set.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.fpl_resume_bgzf_bam.restype = C.c_int
+        L.fpl_resume_bgzf_bam.argtypes = [C.c_void_p]
+        L.fpl_reserve_bam_tail.restype = C.c_int
+        L.fpl_reserve_bam_tail.argtypes = [C.c_void_p, C.c_uint64]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -249,6 +269,63 @@ class Inflater:
 
 def _b(s):
     return s.encode("latin-1") if isinstance(s, str) else bytes(s)
+
+
+class BgzfBatch:
+    """One submission of Engine.submit_bgzf.  Batches are collected in the order of submission, each through its own wait()."""
+
+    def __init__(self, eng, gzip, keep):
+        self.eng, self.gzip, self._keep = eng, gzip, keep
+        self._outs = None
+
+    @staticmethod
+    def _info(win):
+        return {k: int(win[0][k]) for k, _ in abi.BAM_WINDOW_DTYPE}
+
+    def peek(self):
+        """fpl_peek_bgzf_bam: the walk's header as a dict (this must be the oldest BGZF batch that is not started)"""
+        win = np.zeros(1, np.dtype(abi.BAM_WINDOW_DTYPE))
+        self.eng._check(self.eng.L.fpl_peek_bgzf_bam(self.eng.h, win.ctypes.data), "fpl_peek_bgzf_bam")
+        return self._info(win)
+
+    def wait(self, want_reads=True, seq_out=None, qual_out=None):
+        """-> (header dict, records, names as a list of bytes, bases, qualities, gzip member).  want_reads=False: the decoded arrays
+        stay on the device and bases / qualities are None; the member is None unless the batch was submitted with gzip=True.  A
+        refused batch gives its header and nothing else.  seq_out / qual_out: uint8 pinned_array views the decoded reads land in
+        (bases / qualities are then views of them) -- a caller that streams a file gives the same pair again once it is done
+        with a batch, and a pair that is too short for this batch is FplError; without them the batch makes a pair of its own,
+        which is freed when the returned arrays are dropped."""
+        e = self.eng
+        if (seq_out is None) != (qual_out is None):
+            raise FplError("BgzfBatch.wait: seq_out and qual_out go together")
+        if want_reads and self._outs is None:
+            h = self.peek()
+            if h["status"] == abi.FPL_BAMW_OK and h["n_reads"]:
+                if seq_out is not None:
+                    if min(len(seq_out), len(qual_out)) < h["n_bases"] or seq_out.dtype != np.uint8 or qual_out.dtype != np.uint8:
+                        raise FplError("BgzfBatch.wait: seq_out / qual_out are uint8 arrays of at least n_bases = %d bytes" % h["n_bases"])
+                    self._outs = (seq_out, qual_out)
+                else:
+                    self._outs = (e.pinned_array(h["n_bases"] + 1, keep=False), e.pinned_array(h["n_bases"] + 1, keep=False))
+                e._check(e.L.fpl_start_bgzf_bam(e.h, self._outs[0].ctypes.data, self._outs[1].ctypes.data), "fpl_start_bgzf_bam")
+        win = np.zeros(1, np.dtype(abi.BAM_WINDOW_DTYPE))
+        rp, npp, op, gp, gl = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        e._check(e.L.fpl_wait_bgzf_bam(e.h, win.ctypes.data, C.byref(rp), C.byref(npp), C.byref(op), C.byref(gp) if self.gzip else None,
+                                       C.byref(gl) if self.gzip else None), "fpl_wait_bgzf_bam")
+        self._keep = None
+        h = self._info(win)
+        member = (C.string_at(gp.value, gl.value) if gl.value else b"") if self.gzip else None
+        n = h["n_reads"]
+        if h["status"] != abi.FPL_BAMW_OK or n == 0:
+            return h, np.zeros(0, dtype=abi.RESULT_DTYPE), [], None, None, member
+        res = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_uint8)), shape=(n * 36,)).view(abi.RESULT_DTYPE).copy()
+        off = np.ctypeslib.as_array(C.cast(op, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        blob = C.string_at(npp.value, h["name_bytes"]) if h["name_bytes"] else b""
+        names = [blob[int(off[i]):int(off[i + 1])] for i in range(n)]
+        seq = qual = None
+        if self._outs is not None:
+            seq, qual = self._outs[0][:h["n_bases"]], self._outs[1][:h["n_bases"]]
+        return h, res, names, seq, qual, member
 
 
 class Engine:
@@ -360,6 +437,46 @@ class Engine:
                     "fpl_process_bam_async")
         self._bam_gz_flags.append(bool(gzip))
 
+    def submit_bgzf(self, comp, blocks, skip=0, gzip=False):
+        """fpl_process_bgzf_bam_async: the payloads of a BAM's BGZF blocks (uint8, ideally a pinned_array view) and their
+        descriptors (abi.BGZF_BLOCK_DTYPE; fastplong_amd.bgzf.blocks cuts a file into them), `skip` inflated bytes in front of
+        the first record (the first submission of a file only).  Inflate, record walk, decode and the per-read kernels all run
+        on the device -> a BgzfBatch with peek() and wait().  The batch keeps `comp` alive until its wait(); a pinned_array's
+        memory goes with the Engine that made it, so it is not handed to another Engine that outlives that one."""
+        if not hasattr(self.L, "fpl_process_bgzf_bam_async"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_process_bgzf_bam_async")
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        blk = np.array(blocks, dtype=np.dtype(abi.BGZF_BLOCK_DTYPE), copy=True, ndmin=1) if len(blocks) else np.zeros(0, np.dtype(abi.BGZF_BLOCK_DTYPE))
+        if gzip or self._bam_gz_on:  # (the switch is the context's: touched only when it has to change)
+            self._check(self.L.fpl_set_bam_gzip(self.h, int(bool(gzip))), "fpl_set_bam_gzip")
+            self._bam_gz_on = bool(gzip)
+        self._check(self.L.fpl_process_bgzf_bam_async(self.h, comp.ctypes.data if len(comp) else None, len(comp),
+                                                      blk.ctypes.data if len(blk) else None, len(blk), int(skip)), "fpl_process_bgzf_bam_async")
+        return BgzfBatch(self, bool(gzip), (comp, blk))
+
+    def bam_tail(self):
+        """fpl_bam_tail_get: the bytes behind the last whole record of the BGZF submissions so far"""
+        n = C.c_uint64(0)
+        rc = self.L.fpl_bam_tail_get(self.h, None, 0, C.byref(n))
+        if rc == abi.FPL_OK or n.value == 0:
+            self._check(rc, "fpl_bam_tail_get")
+            return b""
+        buf = np.zeros(n.value, np.uint8)
+        self._check(self.L.fpl_bam_tail_get(self.h, buf.ctypes.data, len(buf), C.byref(n)), "fpl_bam_tail_get")
+        return buf[:n.value].tobytes()
+
+    def set_bam_tail(self, data=b""):
+        """fpl_bam_tail_set: replaces the tail and clears the refusal flag; b"" starts a new file"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self._check(self.L.fpl_bam_tail_set(self.h, buf.ctypes.data if len(buf) else None, len(buf)), "fpl_bam_tail_set")
+
+    def resume_bgzf(self):
+        """fpl_resume_bgzf_bam: clears the refusal flag and keeps the tail"""
+        self._check(self.L.fpl_resume_bgzf_bam(self.h), "fpl_resume_bgzf_bam")
+
+    def reserve_bam_tail(self, nbytes):
+        self._check(self.L.fpl_reserve_bam_tail(self.h, int(nbytes)), "fpl_reserve_bam_tail")
+
     def decode_bam(self, bam, rec_start, off):
         """fpl_decode_bam on this engine's device -> (bases, qualities) as uint8 arrays of off[-1] bytes"""
         return decode_bam(self.device, bam, rec_start, off)
@@ -416,8 +533,9 @@ class Engine:
     def in_flight(self):
         return int(self.L.fpl_in_flight(self.h))
 
-    def pinned_array(self, n, dtype=np.uint8):
-        """numpy view of n items of page-locked host memory (fpl_host_alloc); freed when the array is collected"""
+    def pinned_array(self, n, dtype=np.uint8, keep=True):
+        """numpy view of n items of page-locked host memory (fpl_host_alloc).  The memory lives as long as this Engine object;
+        keep=False: only as long as the array and its views do (the library must be done with it by then)."""
         nbytes = max(1, int(n) * np.dtype(dtype).itemsize)
         ptr = self.L.fpl_host_alloc(nbytes)
         if not ptr:
@@ -430,8 +548,11 @@ class Engine:
 
         buf = (C.c_uint8 * nbytes).from_address(ptr)
         arr = np.frombuffer(buf, dtype=dtype, count=int(n))
-        self._pinned = getattr(self, "_pinned", [])
-        self._pinned.append((_Owner(), buf))
+        if keep:
+            self._pinned = getattr(self, "_pinned", [])
+            self._pinned.append((_Owner(), buf))
+        else:
+            buf._owner = _Owner()  # (arr and its views hold buf)
         return arr
 
     def fragments(self):

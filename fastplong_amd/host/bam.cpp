@@ -10,6 +10,7 @@
 #include <atomic>
 
 #include "split.h"
+#include "../csrc/bam_rules.h"
 
 using namespace std;
 
@@ -17,7 +18,7 @@ namespace fplh {
 
 namespace {
 
-constexpr uint64_t MAX_TAG_BYTES = 256u << 20; /* the walk's bound on a record's tags (see walk) */
+namespace rule = fpl::bamrule; /* the record checks, shared with the device's walk (csrc/bam_walk.h) */
 
 inline uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 inline uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -245,16 +246,16 @@ bool BamReader::walk(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint64_t 
             err_ = "BAM record " + to_string(rec_no_) + (with_name ? " (" + name + ")" : string()) + ": " + what;
             return false;
         };
-        if (bs < 32) return fail("block_size " + to_string(bs) + " does not agree with its fields", false);
+        if (!rule::block_size_ok(bs)) return fail("block_size " + to_string(bs) + " does not agree with its fields", false);
         /* the fixed fields first: a damaged block_size must fail here, not make the reader inflate what it claims (up to 4 GiB) */
         if (avail < 36) {
             need_ = 36;
             return true;
         }
-        const uint32_t l_name = r[12], n_cigar = rd16(r + 16), flag = rd16(r + 18), l_seq = rd32(r + 20);
-        const uint64_t fixed = 32 + (uint64_t)l_name + 4 * (uint64_t)n_cigar + ((uint64_t)l_seq + 1) / 2 + l_seq;
+        const rule::Fields f = rule::fields(r);
+        const uint32_t l_name = f.l_name, n_cigar = f.n_cigar, flag = f.flag, l_seq = f.l_seq;
         /* (tags may follow the fields, but not more than MAX_TAG_BYTES + 16 bytes for every byte of them) */
-        if (l_name < 1 || l_seq > 0x7FFFFFFFu || fixed > (uint64_t)bs || (uint64_t)bs - fixed > MAX_TAG_BYTES + 16 * fixed)
+        if (!rule::fields_ok(f))
             return fail("block_size " + to_string(bs) + " does not agree with its fields",
                         l_name >= 1 && 32 + (uint64_t)l_name <= bs && avail >= 36 + (uint64_t)l_name);
         if (avail < 4 + (uint64_t)bs) {
@@ -263,13 +264,13 @@ bool BamReader::walk(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint64_t 
         }
         const uint8_t* name = r + 36;
         const uint8_t* qual = name + l_name + 4 * (size_t)n_cigar + (l_seq + 1) / 2;
-        if (flag & 0x900) { /* secondary / supplementary: not part of the twin */
+        if (rule::skipped(flag)) { /* secondary / supplementary: not part of the twin */
             wpos_ += 4 + (uint64_t)bs;
             rec_no_++;
             continue;
         }
-        if (flag & 0x1) return fail("flag 0x1 (paired-end) -- fastplong is single-end", true);
-        if (l_seq > 0 && qual[0] == 0xFF) return fail("no qualities (the first quality byte is 0xFF)", true);
+        if (rule::paired(flag)) return fail("flag 0x1 (paired-end) -- fastplong is single-end", true);
+        if (rule::no_qualities(f, l_seq ? qual[0] : 0)) return fail("no qualities (the first quality byte is 0xFF)", true);
         const size_t nl = strnlen((const char*)name, l_name - 1);
         const size_t t = b.text.size();
         b.text.resize(t + 1 + nl + 1);

@@ -480,6 +480,99 @@ int fpl_inflate_bgzf(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes
 void fpl_inflater_destroy(fpl_inflater* inf);
 
 /*
+ * A BAM's BGZF blocks in, records out: the inflate, the record walk, the decode and the per-read kernels chained on the device, the
+ * inflated bytes never leaving it (csrc/bgzf_inflate.h -> csrc/bam_walk.h -> csrc/bam_decode.h -> the per-read kernels, and with
+ * fpl_set_bam_gzip on, the gzip kernels).  FPL_ABI_VERSION stays 10: found by symbol lookup; a library without these calls is a
+ * valid v10 library, and the caller then takes fpl_inflate_bgzf / fpl_process_bam_async.
+ *
+ * A BAM record says where the next one starts, and a batch of blocks rarely ends at a record's end: the bytes behind the last whole
+ * record of a submission -- the TAIL -- are kept in the context, on the device, and go in front of the next submission's bytes.
+ * The walk of submission k + 1 is ordered behind that of submission k on the context's parse stream; that order carries the tail,
+ * and no submission waits for a walk.  The rules of a record are the host walk's (csrc/bam_rules.h, host/bam.cpp); the device
+ * words no errors: a submission is taken whole or REFUSED by status, and what is refused the caller takes through the host path.
+ *
+ *   fpl_process_bgzf_bam_async  comp, comp_bytes, blocks, n_blocks: as for fpl_inflate_bgzf (payloads and descriptors; status is
+ *                      not written back), with out_off relative to this submission's inflated bytes.  The blocks must be in order
+ *                      and without gaps: out_off[0] == 0, out_off[i + 1] == out_off[i] + isize[i]; the total is at most 0xFFFFFFF0.
+ *                      Ranges are checked on the calling thread (FPL_ERR_ARG, nothing enqueued).  skip: inflated bytes in front of
+ *                      the first record -- the BAM header, which the caller parses itself; valid only while the context holds no
+ *                      tail as far as the host knows: no submission since fpl_create, since fpl_bam_tail_set(ctx, NULL, 0), or since
+ *                      an fpl_resume_bgzf_bam that found the tail empty (a refused first stretch goes in again with its skip);
+ *                      FPL_ERR_ARG otherwise.  Takes one of the
+ *                      FPL_MAX_IN_FLIGHT slots, FIFO.  The upload goes on the copy stream, inflate and walk on the parse stream
+ *                      behind it; only the 64-byte header comes back.  comp and blocks must stay valid until the batch has been
+ *                      peeked at or waited for.  Contexts with break_enabled / mask_enabled: FPL_ERR_STATE, as for text.
+ *   fpl_peek_bgzf_bam  waits for the header of the oldest such batch that is not started, and fills *out.  Nothing of the batch is
+ *                      counted yet.
+ *   fpl_start_bgzf_bam enqueues the decode and the per-read kernels of that batch.  seq_out, qual_out: page-locked arrays of
+ *                      n_bases bytes (the header's) that get the decoded reads as fpl_process_bam_async's do, or both NULL: the
+ *                      decoded arrays then stay on the device (the stats-only caller, the gzip batch).  One NULL: FPL_ERR_ARG.
+ *                      A refused or empty batch: FPL_OK, nothing to start.
+ *   fpl_wait_bgzf_bam  the oldest batch in flight, which must be of this kind (FPL_ERR_STATE otherwise, as fpl_wait, fpl_wait_text
+ *                      and fpl_wait_bam_gz are for a batch of this kind).  Starts it with NULL arrays if it was not started.  *out
+ *                      is the header; for status FPL_BAMW_OK *results are the n_reads records, *names the name_bytes bytes of all
+ *                      names ('@' + the record's read name up to its NUL, nothing between them) and *name_off n_reads + 1 offsets
+ *                      into them -- library memory, valid until the next submission that takes this batch's slot, as fpl_wait_text
+ *                      documents for its pointers.  gz, gz_len (may be NULL): when fpl_set_bam_gzip was on at submission, the
+ *                      member of fpl_wait_bam_gz.  Any of the pointer arguments but ctx and out may be NULL.
+ *
+ *   status             FPL_BAMW_OK.  FPL_BAMW_BLOCK: a block k_bgzf_inflate did not vouch for, bad_index is the first.
+ *                      FPL_BAMW_RECORD: a record failed a check; bad_index is its index in the file (skipped records counted,
+ *                      from the first submission of the file on) and bad_pos its byte offset in [the tail | this submission's
+ *                      inflated bytes].  FPL_BAMW_TAIL_ROOM: the new tail (tail_bytes) exceeds the context's tail capacity.
+ *                      FPL_BAMW_TOO_MANY: more records than the slot's arrays hold (one per 64 bytes and 1024), or names that
+ *                      take more than a quarter of [tail room | inflated bytes] and 1 MiB.
+ *                      FPL_BAMW_CHAIN: an earlier submission was refused.
+ *                      A refused submission counts nothing, leaves the tail exactly as it was, and sets a flag in device memory
+ *                      that the walks of the submissions already queued behind it read: they refuse with FPL_BAMW_CHAIN.
+ *
+ * Recovery (all three: FPL_ERR_STATE while a batch of this kind is in flight):
+ *   fpl_bam_tail_get   the tail's bytes into buf (cap bytes; *len gets the length, FPL_ERR_ARG with *len set when cap is short).
+ *   fpl_bam_tail_set   replaces the tail and clears the flag; len 0 is a new file (skip is allowed again, record indices restart).
+ *   fpl_resume_bgzf_bam  clears the flag and keeps the tail (an empty one allows skip again): the refused blocks are submitted
+ *                      again, e.g. after
+ *   fpl_reserve_bam_tail  which makes the tail capacity at least `bytes` (before the first submission: exactly `bytes`; the
+ *                      default is FPL_BAM_TAIL_DEFAULT, which holds one record of a 5 Mb read -- a default, not a measured optimum).
+ * Any refused stretch goes through the host path without losing a record: get the tail, inflate the refused blocks behind it and
+ * walk the bytes on the host, hand the whole records to fpl_process_bam_async, set the tail to the rest, and go on.
+ *
+ * Environment (read in fpl_create): FPL_BAM_SEG_BYTES=n cuts the walk into segments of n bytes, not of 64 KiB -- for tests, which
+ * want many segments from a small file; a value below 64 or above 2^30 is ignored.
+ */
+#define FPL_BAM_TAIL_DEFAULT (8u << 20)
+typedef struct fpl_bam_window { /* 64 bytes */
+    uint32_t status;
+    uint32_t n_reads;      /* records taken */
+    uint64_t n_bases;
+    uint32_t max_read_len;
+    uint32_t segments;     /* segments the walk cut the buffer into */
+    uint64_t name_bytes;
+    uint64_t records_seen; /* n_reads and the skipped (secondary / supplementary) ones */
+    uint32_t tail_bytes;
+    uint32_t rewalked;     /* segments whose guess the chain did not prove, walked again serially */
+    uint64_t bad_index;
+    uint64_t bad_pos;
+} fpl_bam_window;
+enum {
+    FPL_BAMW_OK = 0,
+    FPL_BAMW_BLOCK = 1,
+    FPL_BAMW_RECORD = 2,
+    FPL_BAMW_TAIL_ROOM = 3,
+    FPL_BAMW_TOO_MANY = 4,
+    FPL_BAMW_CHAIN = 5
+};
+int fpl_process_bgzf_bam_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_bytes, const fpl_bgzf_block* blocks, uint32_t n_blocks,
+                               uint64_t skip);
+int fpl_peek_bgzf_bam(fpl_ctx* ctx, fpl_bam_window* out);
+int fpl_start_bgzf_bam(fpl_ctx* ctx, uint8_t* seq_out, uint8_t* qual_out);
+int fpl_wait_bgzf_bam(fpl_ctx* ctx, fpl_bam_window* out, const fpl_read_result** results, const uint8_t** names, const uint64_t** name_off,
+                      const uint8_t** gz, uint64_t* gz_len);
+int fpl_bam_tail_get(fpl_ctx* ctx, uint8_t* buf, uint64_t cap, uint64_t* len);
+int fpl_bam_tail_set(fpl_ctx* ctx, const uint8_t* bytes, uint64_t len);
+int fpl_resume_bgzf_bam(fpl_ctx* ctx);
+int fpl_reserve_bam_tail(fpl_ctx* ctx, uint64_t bytes);
+
+/*
  * ONE LONG deflate stream -- the payload of an ordinary one-member .gz -- inflated on the device, a window of compressed bytes per
  * call (csrc/gzip_inflate.h).  FPL_ABI_VERSION stays 10: found by symbol lookup like fpl_inflate_bgzf, on the same handle.
  *

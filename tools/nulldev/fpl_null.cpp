@@ -293,6 +293,20 @@ int fpl_inflate_gzip(fpl_inflater*, const uint8_t*, uint64_t, uint64_t, const ui
     return FPL_ERR_NO_DEVICE;
 }
 void fpl_inflater_destroy(fpl_inflater*) {}
+/* (the resident BAM path is the device's walk: the null device refuses, and a host takes fpl_process_bam_async) */
+int fpl_process_bgzf_bam_async(fpl_ctx*, const uint8_t*, uint64_t, const fpl_bgzf_block*, uint32_t, uint64_t) { return FPL_ERR_NO_DEVICE; }
+int fpl_peek_bgzf_bam(fpl_ctx*, fpl_bam_window*) { return FPL_ERR_STATE; }
+int fpl_start_bgzf_bam(fpl_ctx*, uint8_t*, uint8_t*) { return FPL_ERR_STATE; }
+int fpl_wait_bgzf_bam(fpl_ctx*, fpl_bam_window*, const fpl_read_result**, const uint8_t**, const uint64_t**, const uint8_t**, uint64_t*) {
+    return FPL_ERR_STATE;
+}
+int fpl_bam_tail_get(fpl_ctx*, uint8_t*, uint64_t, uint64_t* len) {
+    if (len) *len = 0;
+    return FPL_ERR_NO_DEVICE;
+}
+int fpl_bam_tail_set(fpl_ctx*, const uint8_t*, uint64_t) { return FPL_ERR_NO_DEVICE; }
+int fpl_resume_bgzf_bam(fpl_ctx*) { return FPL_ERR_NO_DEVICE; }
+int fpl_reserve_bam_tail(fpl_ctx*, uint64_t) { return FPL_ERR_NO_DEVICE; }
 /* (the emitted batch lives in device memory: the null device has none) */
 int fpl_emit_batch_device(fpl_ctx*, const uint8_t*, const uint8_t*, const uint64_t*, uint32_t, const fpl_read_result*, uint8_t*, uint8_t*, uint64_t,
                           uint64_t*, uint32_t, uint32_t*, uint8_t*, fpl_emit_info*, void*) {
