@@ -1,5 +1,5 @@
 /*
- * buf.h -- the host layer's owned buffers: device memory (DevBuf) and page-locked host memory (PinBuf).
+ * buf.h -- what the host layer owns: device memory (DevBuf), page-locked host memory (PinBuf), events and streams (Event, Stream).
  *
  * A buffer is a pointer and the number of elements behind it.  It is freed exactly once (not copyable), its capacity is what
  * was allocated and never shrinks, and a grow empties it before it allocates, so a failed allocation leaves an empty buffer
@@ -94,5 +94,28 @@ template <class T, class Mem>
 hipError_t Buf<T, Mem>::grow(size_t need, size_t extra) {
     return holds(need) ? hipSuccess : regrow(want(grown(need, extra)));
 }
+
+/* An event or a stream of the host layer: empty until create(), destroyed exactly once (not copyable) -- with its owner, so no list
+   of handles has to be kept in step by hand.  It reads as the raw handle wherever a HIP call takes one; `.h` where a void* is made
+   of it (BatchArgs). */
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    ~Handle() { reset(); }
+    void reset() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
+    }
+    operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return reset(), hipEventCreateWithFlags(&h, flags); }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create() { return reset(), hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+};
 
 }  // namespace fpl

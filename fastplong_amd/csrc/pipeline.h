@@ -1,5 +1,5 @@
 /*
- * pipeline.h -- the launch sequence of one batch, shared by the HIP library (fpl_hip.hip)
+ * pipeline.h -- the launch sequence of one batch, shared by the HIP library (rt_batch.h of fpl_hip.hip)
  * and by the test-only emulator driver (tests/emu/emu_driver.cpp) so that grid shapes and
  * kernel order are exercised on the CPU too.
  *

@@ -375,3 +375,113 @@ def test_argument_and_state_errors(engine_mod, files):
     comp, blk, _ = payload(eng, f["data"])
     assert eng.L.fpl_process_bgzf_bam_async(eng.h, comp.ctypes.data, len(comp), blk.ctypes.data, len(blk), 0) == STATE
     eng.close()
+
+
+def text_batch(eng, seed):
+    """200 reads as CSR arrays and as FASTQ text in the engine's page-locked memory"""
+    seq, qual, off = synth.ont_like(200, seed=seed, median_len=1500, max_len=8000)
+    text = hostio.make_fastq(seq, qual, off)[0]
+    buf = eng.pinned_array(len(text))
+    buf[:] = np.frombuffer(text, np.uint8)
+    return seq, qual, off, buf
+
+
+def test_staged_kinds_interleaved(engine_mod, files):
+    """text T1, a BGZF batch B, text T2 in flight together: each kind's peek / start / cancel finds the oldest pending slot of ITS
+    kind, whatever stands in front of it, and the waits collect in the order of submission"""
+    import ctypes as Cc
+    f = files["b300"]
+    t, L, STATE = f["t"], None, abi.FPL_ERR_STATE
+    # what B and T2 alone give: the host path for B, the same reads as a CSR batch for T2, one context
+    ref = new_engine(engine_mod)
+    s2, q2, o2, _ = text_batch(ref, 22)
+    host_path(engine_mod, t, eng=ref)
+    want2 = np.zeros(len(o2) - 1, abi.RESULT_DTYPE)
+    ref.submit_host(s2, q2, o2, want2)
+    ref.wait()
+    want_cnt = ref.counters()
+    ref.close()
+
+    eng = new_engine(engine_mod)
+    L = eng.L
+    _, _, o1, t1 = text_batch(eng, 21)
+    _, _, _, t2 = text_batch(eng, 22)
+    assert int(o1[-1]) != int(o2[-1])
+    comp, blk, _ = payload(eng, f["data"])
+    eng.submit_text(t1)
+    batch = eng.submit_bgzf(comp, blk, skip=bgzf.header_len(f["data"]))
+    eng.submit_text(t2)
+    assert eng.in_flight() == abi.FPL_MAX_IN_FLIGHT == 3
+    info = eng.peek_text()
+    assert info["status"] == abi.FPL_TEXT_OK and info["n_reads"] == 200 and info["n_bases"] == int(o1[-1])  # T1
+    h = batch.peek()  # B, although T1 is older
+    assert h["status"] == abi.FPL_BAMW_OK and h["n_reads"] == t["n"] and not eng.counters().any()
+    nb = int(t["off"][-1])
+    so, qo = eng.pinned_array(nb + 1), eng.pinned_array(nb + 1)
+    assert L.fpl_start_bgzf_bam(eng.h, so.ctypes.data, qo.ctypes.data) == 0  # B's kernels ahead of T1's wait
+    eng.cancel_text()  # T1
+    info = eng.peek_text()
+    assert info["status"] == abi.FPL_TEXT_OK and info["n_reads"] == 200 and info["n_bases"] == int(o2[-1])  # T2
+    # a fourth submission, of any kind
+    r4 = np.zeros(len(o2) - 1, abi.RESULT_DTYPE)
+    raw = np.frombuffer(t["raw"], np.uint8)
+    assert L.fpl_process_text_async(eng.h, t2.ctypes.data, len(t2)) == STATE
+    assert L.fpl_process_bgzf_bam_async(eng.h, comp.ctypes.data, len(comp), blk.ctypes.data, len(blk), 0) == STATE
+    assert L.fpl_process_batch_async(eng.h, s2.ctypes.data, q2.ctypes.data, o2.ctypes.data, len(o2) - 1, r4.ctypes.data) == STATE
+    assert L.fpl_process_bam_async(eng.h, raw.ctypes.data, len(raw), t["rec"].ctypes.data, t["off"].ctypes.data, 0, None, None, None) == STATE
+    assert eng.in_flight() == 3
+    # the waits, in the order of submission
+    info, res, _ = eng.wait_text()
+    assert info["status"] == abi.FPL_TEXT_CANCELLED and len(res) == 0
+    got = batch.wait(want_reads=False)  # (started above, into so / qo)
+    assert_same(got, t, f["ref"], arrays=False)
+    assert so[:nb].tobytes() == f["ref"]["seq"].tobytes() and qo[:nb].tobytes() == f["ref"]["qual"].tobytes()
+    info, res, _ = eng.wait_text()
+    assert info["status"] == abi.FPL_TEXT_OK and info["n_reads"] == 200 and res.tobytes() == want2.tobytes()
+    assert np.array_equal(eng.counters(), want_cnt)  # B and T2, nothing of T1
+    # nothing in flight: nothing pending for either kind
+    assert eng.in_flight() == 0
+    fr = abi.FplTextResult()
+    win = np.zeros(1, np.dtype(abi.BAM_WINDOW_DTYPE))
+    assert L.fpl_peek_text(eng.h, Cc.byref(fr)) == STATE and L.fpl_start_text(eng.h) == STATE and L.fpl_cancel_text(eng.h) == STATE
+    assert L.fpl_peek_bgzf_bam(eng.h, win.ctypes.data) == STATE and L.fpl_start_bgzf_bam(eng.h, None, None) == STATE
+    eng.close()
+
+
+def test_check_order_of_the_submit_calls_with_break(engine_mod, files):
+    """break_enabled: the staged kinds are refused outright, the CSR and BAM calls only while a batch is in flight; an argument
+    error comes before either"""
+    f = files["b300"]
+    t = f["t"]
+    eng = new_engine(engine_mod, break_enabled=1)
+    L, ARG, STATE = eng.L, abi.FPL_ERR_ARG, abi.FPL_ERR_STATE
+    seq, qual, off, tbuf = text_batch(eng, 23)
+    n = len(off) - 1
+    comp, blk, _ = payload(eng, f["data"])
+    raw = np.frombuffer(t["raw"], np.uint8)
+    nb = int(t["off"][-1])
+    so, qo = eng.pinned_array(nb + 1), eng.pinned_array(nb + 1)
+    rb = np.zeros(t["n"], abi.RESULT_DTYPE)
+    r0, r1 = np.zeros(n, abi.RESULT_DTYPE), np.zeros(n, abi.RESULT_DTYPE)
+
+    def csr(res):
+        return L.fpl_process_batch_async(eng.h, seq.ctypes.data, qual.ctypes.data, off.ctypes.data, n, res.ctypes.data if res is not None else None)
+
+    def bam(res):
+        return L.fpl_process_bam_async(eng.h, raw.ctypes.data, len(raw), t["rec"].ctypes.data, t["off"].ctypes.data, t["n"], so.ctypes.data,
+                                       qo.ctypes.data, res.ctypes.data if res is not None else None)
+
+    assert L.fpl_process_text_async(eng.h, tbuf.ctypes.data, len(tbuf)) == STATE
+    assert L.fpl_process_bgzf_bam_async(eng.h, comp.ctypes.data, len(comp), blk.ctypes.data, len(blk), bgzf.header_len(f["data"])) == STATE
+    assert csr(None) == ARG and bam(None) == ARG and eng.in_flight() == 0
+    assert csr(r0) == 0 and eng.in_flight() == 1
+    eng._bam_gz_flags.append(False)  # (what submit_host notes for wait())
+    assert csr(r1) == STATE and bam(rb) == STATE  # one in flight: the fragment lists are its
+    assert csr(None) == ARG and bam(None) == ARG and eng.in_flight() == 1
+    assert L.fpl_set_bam_gzip(eng.h, 1) == STATE
+    eng.wait()
+    assert eng.in_flight() == 0 and csr(r1) == 0  # collected: the next one is let in
+    eng._bam_gz_flags.append(False)
+    eng.wait()
+    assert r1.tobytes() == r0.tobytes()
+    eng.close()
