@@ -4,7 +4,7 @@
  *
  * fpl_process_batch_device leaves one record per read; what a writer makes of the records -- every fragment with code
  * FPL_PASS_FILTER of every read that was not dropped, in input order, fragment 0 before fragment 1 (format_range,
- * host/fastq.cpp) -- these kernels make where the bases are, so that a second device-side consumer never meets the host:
+ * host/format.cpp) -- these kernels make where the bases are, so that a second device-side consumer never meets the host:
  *
  *   k_emit_count   lane = read: its passing fragments and their bytes; per block of EM_LAYOUT_READS reads the sums, the
  *                  longest fragment and whether a window reaches outside its read

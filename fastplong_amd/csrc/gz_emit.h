@@ -6,7 +6,7 @@
  * nl_pos[]: GzTextSrc), or a BAM batch's record bytes, record starts, decoded bases / qualities and CSR offsets (bam_decode.h:
  * GzBamSrc).  k_gz_layout / k_gz_compose are the text forms and k_gz_layout_bam / k_gz_compose_bam the BAM forms of ONE body each,
  * templated on the source, so the cuts and the length arithmetic exist once.  Output: one
- * gzip member (RFC 1952) whose inflation is exactly what fplh::format_batch (host/fastq.cpp, format_range without a fragment
+ * gzip member (RFC 1952) whose inflation is exactly what fplh::format_batch (host/format.cpp, format_range without a fragment
  * list) appends for that batch; nothing at all when no read passed.  Long-read FASTQ has next to nothing for LZ77 to find, so the
  * deflate stream holds literals only: the gain is the entropy code, and blocks are cut so that bases and qualities -- which share
  * byte values -- mostly get tables of their own.

@@ -9,7 +9,8 @@
 #include <algorithm>
 #include <atomic>
 
-#include "split.h"
+#include "gzip.h"
+#include "pool.h"
 #include "../csrc/bam_rules.h"
 
 using namespace std;

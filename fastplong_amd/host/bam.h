@@ -21,7 +21,8 @@
 #include <string>
 #include <vector>
 
-#include "fastq.h"
+#include "batch.h"
+#include "fastplong_amd.h"
 
 namespace fplh {
 

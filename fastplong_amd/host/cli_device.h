@@ -7,7 +7,7 @@
 
 #include "bam.h"
 #include "cli_options.h"
-#include "fastq.h"
+#include "gzip.h"
 
 /* The optional entry points.  They are looked up at run time: the binary must start against a library without them (the
    test stand-ins, an older build).  Which of them a run NEEDS is the caller's business: BAM input without the two v8 calls
@@ -28,7 +28,7 @@ struct DeviceApi {
     InflaterCreateFn inflater_create = nullptr;
     fplh::BgzfInflateFn inflate_bgzf = nullptr;
     InflaterDestroyFn inflater_destroy = nullptr;
-    fplh::GzipInflateFn inflate_gzip = nullptr; /* (the same handle: a one-member .gz, host/fastq.h) */
+    fplh::GzipInflateFn inflate_gzip = nullptr; /* (the same handle: a one-member .gz, host/gzip.h) */
     /* --out *.gz deflated on the device: text batches (version 9), BAM-backed batches (version 10) */
     SetGzipFn set_text_gzip = nullptr;
     WaitTextGzFn wait_text_gz = nullptr;

@@ -5,6 +5,7 @@
 #ifndef FPLH_CLI_FINISH_H
 #define FPLH_CLI_FINISH_H
 
+#include "batch.h"
 #include "cli_pipeline.h"
 
 /* --verbose: where the wall time of the host pipeline went (busy seconds per stage), and which paths the batches took */

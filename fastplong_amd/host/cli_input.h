@@ -9,6 +9,8 @@
 #include "cli_device.h"
 #include "evaluator.h"
 #include "fastq.h"
+#include "gzip.h"
+#include "pool.h"
 
 struct InputFacts {
     bool bam = false;         /* BAM input (host/bam.h): recognised by its content; its bases are decoded on the device */
@@ -37,7 +39,7 @@ static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
         }
     }
     /* --device_inflate on a gzip FILE: the single-member lane of the in-memory expansion hands its member to the first device
-       window by window (fpl_inflate_gzip; host/fastq.h set_gzip_inflater).  The multi-member lane, --gz_stream and pipes never
+       window by window (fpl_inflate_gzip; host/gzip.h set_gzip_inflater).  The multi-member lane, --gz_stream and pipes never
        come near it.  A library without the call: the host inflates, silently. */
     if (opt.deviceInflate && !in.bam && !opt.from_stdin && !opt.gzStream && api.inflater_create && api.inflate_gzip && api.inflater_destroy) {
         unsigned char magic[2] = {0, 0};

@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "fastplong_amd.h"
-#include "split.h"
+#include "fasta.h"
 
 using namespace std;
 

@@ -6,7 +6,9 @@
 #define FPLH_CLI_OUTPUT_H
 
 #include "cli_options.h"
-#include "fastq.h"
+#include "gzip.h"
+#include "pool.h"
+#include "split.h"
 
 /* Outputs are plain files; a name ending in .gz gets gzip members (-z level), one per formatted slice,
    deflated on the formatter threads and concatenated by the writer: any gzip reader takes that as one stream */

@@ -10,7 +10,9 @@
 
 #include "cli_input.h"
 #include "cli_output.h"
+#include "fastq.h"
 #include "report.h"
+#include "split.h"
 
 /* One batch on its way through the host pipeline:
  *   reader thread (parse into CSR) -> one thread per device (fpl_process_batch, then the output text on a few

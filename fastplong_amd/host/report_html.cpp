@@ -14,7 +14,7 @@
 #include <thread>
 #include <type_traits>
 
-#include "fastq.h"
+#include "pool.h"
 #include "report.h"
 #include "report_internal.h"
 

@@ -1,75 +1,21 @@
 /*
- * split.h -- gzip members for the output files and the --split / --split_by_lines writer
+ * split.h -- the --split / --split_by_lines writer
  * (reference src/threadconfig.cpp:72-120, src/seprocessor.cpp:297-316), shared by the CLI and the host tests.
  */
 #ifndef FPLH_SPLIT_H
 #define FPLH_SPLIT_H
 
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <sys/uio.h>
 
-#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <functional>
-#include <map>
 #include <mutex>
-#include <ostream>
 #include <string>
 #include <thread>
 #include <vector>
 
 namespace fplh {
-
-/* one complete gzip member holding `in` (any gzip reader takes a concatenation of members as one stream).  Whole-buffer
- * work: libdeflate does it (the library the reference's Writer uses, src/writer.cpp:110-133; loaded at run time when
- * the system has libdeflate.so.0), zlib otherwise. */
-void gzip_into(const std::string& in, int level, std::string& out);
-std::string gzip_member(const std::string& in, int level);
-/* bytes without std::vector's zero fill (an inflate target is overwritten anyway, and its size is a guess) */
-struct RawBuf {
-    char* p = nullptr;
-    size_t n = 0, cap = 0;
-    RawBuf() = default;
-    RawBuf(const RawBuf&) = delete;
-    RawBuf& operator=(const RawBuf&) = delete;
-    RawBuf(RawBuf&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr, o.n = o.cap = 0; }
-    RawBuf& operator=(RawBuf&& o) noexcept {
-        swap(o);
-        return *this;
-    }
-    ~RawBuf() { free(p); }
-    void swap(RawBuf& o) {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        std::swap(cap, o.cap);
-    }
-    void reserve(size_t c) {
-        if (c > cap) {
-            p = (char*)realloc(p, c);
-            cap = c;
-        }
-    }
-    void release() {
-        free(p);
-        p = nullptr;
-        n = cap = 0;
-    }
-    char* data() { return p; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    void clear() { n = 0; }
-};
-/* the gzip member that starts at in[0]: inflated into out, *consumed = its compressed length.  hint = a guess of the
-   inflated size (0 = none).  1 = a whole member, 0 = not a (complete, undamaged) member, 2 = it inflates to more than
-   cap bytes */
-int gunzip_member(const unsigned char* in, size_t in_len, RawBuf& out, size_t cap, size_t* consumed, size_t hint = 0);
-bool have_libdeflate();
-/* one whole member straight into caller-owned memory (libdeflate only): 1 = done (*consumed input bytes, *produced output
-   bytes), 2 = out_cap is too small, 0 = damaged / truncated, -1 = libdeflate is not there */
-int gunzip_member_into(const unsigned char* in, size_t in_len, char* out, size_t out_cap, size_t* consumed, size_t* produced);
 
 /* --split / --split_by_lines.  Each of the reference's workers owns a writer and walks through the file numbers
  * t, t + T, t + 2T, ... as its current file fills up (ThreadConfig::initWriterForSplit / markProcessed /
@@ -139,21 +85,5 @@ class SplitOutput {
     bool closed_ = false;
 };
 
-/* --adapter_fasta: FastaReader + Options::loadFastaAdapters (src/fastareader.cpp:5-101, src/options.cpp:39-66).
- * load_fasta_contigs restates the reader byte for byte (pinned against the real FastaReader, tests/test_host_split.py);
- * load_fasta_adapters keeps the sequences of >= 6 characters in header order -- the order trimByMultiSequences visits
- * them in -- and reports the skipped ones on `log` like the reference.  false + err when the file cannot be read. */
-bool load_fasta_contigs(const std::string& path, std::map<std::string, std::string>& contigs, std::string& err);
-bool load_fasta_adapters(const std::string& path, std::vector<std::string>& adapters, std::ostream* log, std::string& err);
-
 }  // namespace fplh
-
-extern "C" {
-/* test hook: "header\tsequence\n" for every contig in map order; malloc'ed, free with fplh_free */
-int fplh_load_fasta(const char* path, char** out, unsigned long long* out_len);
-/* test hook: replay n_packs packs (worker, reads, passing reads, text) through a SplitOutput; returns the number of
-   files it opened */
-int fplh_split_replay(const char* out, int digits, int workers, int by_lines, int number, long size, int gz_level,
-                      unsigned n_packs, const int* worker, const long* reads, const long* passed, const char* const* texts);
-}
 #endif

@@ -1,4 +1,4 @@
-"""The single-member lane of the host's gzip expansion with an inflater hook (host/fastq.h: set_gzip_inflater), through the test
+"""The single-member lane of the host's gzip expansion with an inflater hook (host/gzip.h: set_gzip_inflater), through the test
 hooks with a ctypes callback backed by Python's zlib: whatever the callback does -- vouch for every window, refuse every third,
 refuse all, fail --, the lane gives the memory it gives without one, and a damaged file is reported by the same reader with the
 same words."""

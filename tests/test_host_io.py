@@ -1,5 +1,5 @@
 """Host side of the path on the CPU: FASTQ -> CSR batches, result records -> output FASTQ text
-(fastplong_amd/host/fastq.cpp), and the record formats pinned against the real reference
+(fastplong_amd/host/fastq.cpp, gzip.cpp, format.cpp), and the record formats pinned against the real reference
 Read::breakByGap / appendToString / appendToStringWithTag (oracle/_ref)."""
 import ctypes as C
 import gzip
@@ -435,6 +435,75 @@ def test_chunk_loader_cuts_the_text_at_records(hostlib, tmp_path, monkeypatch, v
         assert (r[:, 1] > r[:, 0]).all()
         if chunk < 10 ** 6:
             assert n > 3
+
+
+@pytest.mark.parametrize("source", ["file", "memory"])
+def test_chunk_window_ends_inside_a_header(hostlib, tmp_path, monkeypatch, source):
+    """a record of several megabytes that starts right behind a chunk cut: the '@' line is inside the window the chunk read, the
+    lines that would validate it are not -- the loader has to read on (a header it cannot check is no reason to cut the text
+    there or to skip it), the parser has to come back with a larger window; both end up with the sequential reader's records"""
+    if source == "memory":
+        monkeypatch.setenv("FPLH_CHUNK_MEM", "1")
+    chunk = 1 << 20
+    small = b"".join(b"@s%d\n%s\n+\n%s\n" % (i, b"ACGT" * 50, b"I" * 200) for i in range(2400))
+    assert len(small) < chunk - 2000
+    n = (chunk + 20 - len(small)) // 2  # the last small record ends just behind the cut, its quality line lies across it
+    big = 4 * chunk + chunk // 2
+    text = small + b"@last\n%s\n+\n%s\n" % (b"C" * n, b"I" * n)
+    big_at = len(text)
+    assert chunk < big_at < chunk + 64
+    text += b"@big\n%s\n+\n%s\n" % (b"G" * big, b"J" * big)
+    tail_at = len(text)
+    text += b"".join(b"@t%d\nACGTACGT\n+\nIIIIIIII\n" % i for i in range(5))
+    p = tmp_path / "in.fq"
+    p.write_bytes(text)
+    hostlib.fplh_text_chunk_ranges.restype = C.c_int64
+    hostlib.fplh_text_chunk_ranges.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_uint64]
+    buf = (C.c_uint64 * 64)()
+    got = hostlib.fplh_text_chunk_ranges(str(p).encode(), chunk, 2, buf, 32)
+    r = np.frombuffer(buf, np.uint64)[:2 * max(got, 0)].reshape(-1, 2).astype(np.int64)
+    assert got == 3 and r.tolist() == [[0, big_at], [big_at, tail_at], [tail_at, len(text)]]
+    want = _read_all(hostlib, p, 2 ** 62, 2 ** 30)
+    assert len(want[2]) - 1 == 2400 + 2 + 5
+    hostlib.fplh_batch_read_chunked.restype = C.c_void_p
+    hostlib.fplh_batch_read_chunked.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    redo = C.c_uint64(0)
+    b = hostlib.fplh_batch_read_chunked(str(p).encode(), chunk, 2, C.byref(redo))
+    assert b
+    nr, nb = hostlib.fplh_batch_n(b), hostlib.fplh_batch_bytes(b)
+    s2 = np.ctypeslib.as_array(C.cast(hostlib.fplh_batch_seq(b), C.POINTER(C.c_uint8)), (nb,)).copy()
+    q2 = np.ctypeslib.as_array(C.cast(hostlib.fplh_batch_qual(b), C.POINTER(C.c_uint8)), (nb,)).copy()
+    o2 = np.ctypeslib.as_array(C.cast(hostlib.fplh_batch_off(b), C.POINTER(C.c_uint64)), (nr + 1,)).copy()
+    hostlib.fplh_batch_free(b)
+    assert np.array_equal(o2, want[2]) and np.array_equal(s2, want[0]) and np.array_equal(q2, want[1])
+
+
+def test_gzip_file_too_short_for_the_fast_lanes(hostlib, tmp_path):
+    """a .gz of fewer bytes than the member chain (64) or the single-member lane (18) looks at is left to zlib's stream, which
+    reads it like any other; bytes that are not even a whole header are no member for the in-memory lane"""
+    text = b"@r\nACGT\n+\nIIII\n"
+    blob = _gz_member(text)
+    assert 18 <= len(blob) < 64
+    p = tmp_path / "tiny.fq.gz"
+    p.write_bytes(blob)
+    seq, qual, off = _read_all(hostlib, p, 10 ** 9, 2 ** 30)
+    assert bytes(seq) == b"ACGT" and bytes(qual) == b"IIII" and off.tolist() == [0, 4]
+    # two members in fewer than 64 bytes: the member chain would follow them, the size rule leaves them to the stream
+    two = blob + _gz_member(b"")
+    assert len(two) < 64
+    p2 = tmp_path / "two.fq.gz"
+    p2.write_bytes(two)
+    hostlib.fplh_gz_members.restype = C.c_uint64
+    hostlib.fplh_gz_members()
+    seq, qual, off = _read_all(hostlib, p2, 10 ** 9, 2 ** 30)
+    assert bytes(seq) == b"ACGT" and off.tolist() == [0, 4] and hostlib.fplh_gz_members() == 0
+    hostlib.fplh_gunzip_to_memory.restype = C.c_void_p
+    hostlib.fplh_gunzip_to_memory.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    size, reserved = C.c_uint64(0), C.c_uint64(0)
+    stub = tmp_path / "stub.fq.gz"
+    stub.write_bytes(blob[:10])
+    assert not hostlib.fplh_gunzip_to_memory(str(stub).encode(), 4, 2 ** 32, C.byref(size), C.byref(reserved))
+    assert not hostlib.fplh_gunzip_to_memory(str(tmp_path / "absent.fq.gz").encode(), 4, 2 ** 32, C.byref(size), C.byref(reserved))
 
 
 def test_truncated_gzip_is_an_error(hostlib, tmp_path):
