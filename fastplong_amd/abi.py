@@ -180,6 +180,18 @@ FPL_BAMW_TOO_MANY = 4
 FPL_BAMW_CHAIN = 5
 FPL_BAM_TAIL_DEFAULT = 8 << 20
 
+# struct fpl_text_window (64 bytes): the header of a BGZF text batch (fpl_peek_bgzf_text / fpl_wait_bgzf_text); status: FPL_TXTW_*
+TEXT_WINDOW_DTYPE = [("status", "<u4"), ("n_reads", "<u4"), ("n_bases", "<u8"), ("max_read_len", "<u4"), ("n_lines", "<u4"),
+                     ("name_bytes", "<u8"), ("records_seen", "<u8"), ("tail_bytes", "<u4"), ("reserved", "<u4"), ("bad_index", "<u8"),
+                     ("bad_pos", "<u8")]
+FPL_TXTW_OK = 0
+FPL_TXTW_BLOCK = 1
+FPL_TXTW_IRREGULAR = 2
+FPL_TXTW_TAIL_ROOM = 3
+FPL_TXTW_TOO_MANY = 4
+FPL_TXTW_CHAIN = 5
+FPL_TXTW_STRAND = 6
+
 # struct fpl_emit_info (32 bytes, device memory): what fpl_emit_batch_device says about the batch it made
 EMIT_INFO_DTYPE = [("n_bytes", "<u8"), ("n_out", "<u4"), ("max_len", "<u4"), ("status", "<u4"), ("reserved", "<u4", (3,))]
 FPL_EMIT_BAD_WINDOW = 1  # status bit 0: a fragment window reaches outside its read

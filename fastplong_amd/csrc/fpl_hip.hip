@@ -29,6 +29,7 @@
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
 #include "bam_walk.h"
+#include "text_walk.h"
 #include "gzip_inflate.h"
 #include "emit.h"
 
@@ -42,6 +43,7 @@ extern "C" {
 #include "rt_slots.h"
 #include "rt_text.h"
 #include "rt_bam.h"
+#include "rt_bgzf_text.h"
 #include "rt_inflater.h"
 #include "rt_merge.h"
 #include "rt_misc.h"

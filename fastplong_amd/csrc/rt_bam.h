@@ -114,9 +114,10 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
 }
 
 /* ---- BGZF blocks in, records out: bgzf_inflate.h -> bam_walk.h -> bam_decode.h -> the per-read kernels ---- */
+/* a batch of either kind that carries the tail (BGZF BAM, BGZF text) is in flight */
 static bool bgzf_in_flight(const fpl_ctx* ctx) {
     for (u32 k = ctx->waited; k != ctx->submitted; k++)
-        if (ctx->slot[k % FPL_MAX_IN_FLIGHT].kind == BatchKind::BGZF) return true;
+        if (bgzf_kind(ctx->slot[k % FPL_MAX_IN_FLIGHT].kind)) return true;
     return false;
 }
 /* k_bgzf_inflate's grid: a wave per block; as many workgroups as the device keeps resident (the tables' LDS bounds them), the rest
@@ -166,6 +167,10 @@ int fpl_process_bgzf_bam_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_
     if (!ctx || (n_blocks && !blocks) || (comp_bytes && !comp)) return FPL_ERR_ARG;
     fpl_ctx::Slot* slp;
     FPL_TRY(slot_begin(ctx, BatchKind::BGZF, ctx->bam_gzip, slp));
+    if (!ctx->bam_fresh && ctx->tail_kind != BatchKind::BGZF) {
+        ctx->err = "fpl_process_bgzf_bam_async: the context holds the tail of BGZF text submissions";
+        return FPL_ERR_STATE;
+    }
     if (skip && !ctx->bam_fresh) {
         ctx->err = "fpl_process_bgzf_bam_async: skip is valid only while the context holds no tail";
         return FPL_ERR_ARG;
@@ -237,7 +242,10 @@ int fpl_process_bgzf_bam_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_
         return FPL_OK;
     };
     const int r = slot_commit(ctx, sl, enqueue(), 1);
-    if (r == FPL_OK) ctx->bam_fresh = false;
+    if (r == FPL_OK) {
+        ctx->bam_fresh = false;
+        ctx->tail_kind = BatchKind::BGZF;
+    }
     return r;
 }
 
@@ -300,7 +308,8 @@ int fpl_wait_bgzf_bam(fpl_ctx* ctx, fpl_bam_window* out, const fpl_read_result**
     return FPL_OK;
 }
 
-/* (the recovery calls run with no BGZF batch in flight: every walk is done -- its header was waited for -- and the state is at rest) */
+/* (the recovery calls, shared by the BGZF BAM and the BGZF text path, run with no batch of either kind in flight: every walk is
+   done -- its header was waited for -- and the state is at rest) */
 int fpl_bam_tail_get(fpl_ctx* ctx, uint8_t* buf, uint64_t cap, uint64_t* len) {
     if (!ctx || !len) return FPL_ERR_ARG;
     *len = 0;

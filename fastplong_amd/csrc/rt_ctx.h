@@ -3,9 +3,14 @@
 #pragma once
 
 /* what a slot holds: a CSR batch (fpl_process_batch_async), a FASTQ text chunk (fpl_process_text_async) or BAM records
-   (fpl_process_bam_async), or a BAM's BGZF blocks whose records the device finds itself (fpl_process_bgzf_bam_async).  fpl_wait /
-   fpl_wait_bam_gz collect CSR and BAM batches, fpl_wait_text* text batches, fpl_wait_bgzf_bam BGZF batches. */
-enum class BatchKind { CSR, Text, BAM, BGZF };
+   (fpl_process_bam_async), a BAM's BGZF blocks whose records the device finds itself (fpl_process_bgzf_bam_async), or a FASTQ's
+   BGZF blocks whose text the device cuts and parses itself (fpl_process_bgzf_text_async).  fpl_wait / fpl_wait_bam_gz collect CSR
+   and BAM batches, fpl_wait_text* text batches, fpl_wait_bgzf_bam BGZF batches, fpl_wait_bgzf_text BGZF text batches. */
+enum class BatchKind { CSR, Text, BAM, BGZF, BGZFText };
+/* the kinds whose submission enqueues stage 1 only (rt_slots.h) */
+static inline bool staged_kind(BatchKind k) { return k == BatchKind::Text || k == BatchKind::BGZF || k == BatchKind::BGZFText; }
+/* the kinds that carry a tail in the context from one submission to the next */
+static inline bool bgzf_kind(BatchKind k) { return k == BatchKind::BGZF || k == BatchKind::BGZFText; }
 /* the slot holds BAM records on the device: d_bam, d_rec and the decoded arrays (what the BAM forms of the gzip kernels read) */
 static inline bool bam_records(BatchKind k) { return k == BatchKind::BAM || k == BatchKind::BGZF; }
 
@@ -95,6 +100,15 @@ struct fpl_ctx {
             DevBuf<TextHeader> d_hdr;
             PinBuf<TextHeader> h_hdr;
             PinBuf<u32> h_line;     /* four line starts per record */
+            /* a BGZF TEXT batch (csrc/text_walk.h): d_text is [room for the tail | the inflated bytes], positions in d_nl / d_line
+               are offsets into it -- what the text forms of the gzip kernels read, as for a text batch; the compressed bytes, the
+               block table, the names and their offsets are Bam's below.  Stage 1 (upload, inflate, the walk, the header's way
+               back) is enqueued at submission, stage 2 (the per-read kernels, the way back of records, names and -- where asked
+               for -- bases and qualities) once the header is in, by fpl_start_bgzf_text or by the wait */
+            DevBuf<u32> d_nlen;
+            DevBuf<TextWalkScratch> d_ws;
+            DevBuf<fpl_text_window> d_whdr;
+            PinBuf<fpl_text_window> h_whdr;
         } text;
         /* a GZIP batch (fpl_set_text_gzip / fpl_set_bam_gzip; csrc/gz_emit.h).  The layout is enqueued behind the per-read kernels
            (submit_tail); everything behind it is sized by what the layout found and enqueued by the wait (gz_emit).  The BAM forms
@@ -152,11 +166,13 @@ struct fpl_ctx {
     uint64_t forms[6] = {0, 0, 0, 0, 0, 0}; /* fpl_get_batch_forms */
     bool text_gzip = false;    /* fpl_set_text_gzip */
     bool bam_gzip = false;     /* fpl_set_bam_gzip */
-    /* fpl_process_bgzf_bam_async: the tail between two submissions and the walk's state live on the device (csrc/bam_walk.h) */
+    /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the
+       device (csrc/bam_walk.h, csrc/text_walk.h) */
     DevBuf<BamWalkState> d_bamw_state;
     DevBuf<u8> d_bam_tail;
     uint64_t bam_tail_cap = FPL_BAM_TAIL_DEFAULT;
     bool bam_fresh = true;     /* the context holds no tail as far as the host knows (no submission since it last looked): skip is allowed */
+    BatchKind tail_kind = BatchKind::BGZF; /* whose tail it is while not fresh: the BGZF kind that submitted last */
     u32 bam_seg_bytes = 0;     /* FPL_BAM_SEG_BYTES (read in fpl_create; 0: BAMW_DEFAULT_SEG) */
     uint64_t gz_batches = 0;   /* fpl_get_gzip_batches */
     std::string err;

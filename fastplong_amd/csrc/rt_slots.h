@@ -1,5 +1,5 @@
-/* rt_slots.h -- the asynchronous path's queue of FPL_MAX_IN_FLIGHT slots, written once for all four kinds: a submission takes the
-   next slot (slot_begin) and counts once its work is enqueued (slot_commit); a staged kind -- text, BGZF -- enqueues stage 1 there
+/* rt_slots.h -- the asynchronous path's queue of FPL_MAX_IN_FLIGHT slots, written once for all five kinds: a submission takes the
+   next slot (slot_begin) and counts once its work is enqueued (slot_commit); a staged kind -- text, BGZF, BGZF text -- enqueues stage 1 there
    and stage 2 (slot_continue) on its start call or in its wait; the waits collect in the order of submission (wait_front,
    wait_staged, wait_finish).  Around them what every kind shares: the slot's staging, the second half of a submission
    (submit_tail), the gzip member of a batch -- and the CSR kind itself. */
@@ -161,7 +161,7 @@ static inline bool read_len_ok(const uint64_t* off, u32 i, u32& max_len) {
 static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out) {
     if (ctx->submitted - ctx->waited >= FPL_MAX_IN_FLIGHT) return FPL_ERR_STATE;
     FPL_HIP(hipSetDevice(ctx->device));
-    const bool staged = kind == BatchKind::Text || kind == BatchKind::BGZF;
+    const bool staged = staged_kind(kind);
     if (ctx->hcfg.defer && (staged || ctx->submitted != ctx->waited)) return FPL_ERR_STATE;
     /* (the slot's previous batch has been waited for -- FPL_MAX_IN_FLIGHT slots, FIFO -- so its buffers are free) */
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
@@ -212,18 +212,20 @@ static int peek_pending(fpl_ctx* ctx, BatchKind kind, fpl_ctx::Slot*& sl, void* 
     return FPL_OK;
 }
 
-/* Stage 2 of a staged batch: the header is in -- enqueue what it sizes (rt_text.h, rt_bam.h; both leave n_reads at 0 where there is
+/* Stage 2 of a staged batch: the header is in -- enqueue what it sizes (rt_text.h, rt_bam.h, rt_bgzf_text.h; all leave n_reads at 0 where there is
    nothing to run: the wait reports).  A no-op for a slot whose stage 2 ran. */
 /* (called by the start calls and the waits only: a submission never waits for a parse, so the next chunk's copy goes out behind this
    one's at once -- no round trip to the host between two chunks on the link -- and a batch that has only been peeked at is in no counter) */
 static int text_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl);
 static int bgzf_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint8_t* seq_out, uint8_t* qual_out);
+static int bgzf_text_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint8_t* seq_out, uint8_t* qual_out);
 static int slot_continue(fpl_ctx* ctx, fpl_ctx::Slot& sl, uint8_t* seq_out, uint8_t* qual_out) {
     if (sl.stage != 1) return FPL_OK;
     sl.stage = 2;
     FPL_HIP(hipEventSynchronize(sl.ev_parsed));
     sl.n_reads = 0;
-    return sl.kind == BatchKind::Text ? text_continue(ctx, sl) : bgzf_continue(ctx, sl, seq_out, qual_out);
+    if (sl.kind == BatchKind::Text) return text_continue(ctx, sl);
+    return sl.kind == BatchKind::BGZF ? bgzf_continue(ctx, sl, seq_out, qual_out) : bgzf_text_continue(ctx, sl, seq_out, qual_out);
 }
 /* fpl_start_*: stage 2 of the pending slot, ahead of its wait; an error here is what that wait reports */
 static int start_pending(fpl_ctx* ctx, BatchKind kind, uint8_t* seq_out, uint8_t* qual_out) {
@@ -268,7 +270,7 @@ int fpl_in_flight(const fpl_ctx* ctx) { return ctx ? (int)(ctx->submitted - ctx-
 static int wait_batch(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx) return FPL_ERR_ARG;
     fpl_ctx::Slot* slp;
-    FPL_TRY(wait_front(ctx, kind_bit(BatchKind::CSR) | kind_bit(BatchKind::BAM), slp)); /* (the others: fpl_wait_text, fpl_wait_bgzf_bam) */
+    FPL_TRY(wait_front(ctx, kind_bit(BatchKind::CSR) | kind_bit(BatchKind::BAM), slp)); /* (the others: fpl_wait_text, fpl_wait_bgzf_bam, fpl_wait_bgzf_text) */
     fpl_ctx::Slot& sl = *slp;
     ctx->waited++;
     if (sl.rc != FPL_OK) return sl.rc; /* nothing was enqueued behind the failure */

@@ -30,6 +30,7 @@ EXPORTS = [
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
     "fpl_resume_bgzf_bam", "fpl_reserve_bam_tail",
+    "fpl_process_bgzf_text_async", "fpl_peek_bgzf_text", "fpl_start_bgzf_text", "fpl_wait_bgzf_text",
 ]
 
 
@@ -187,6 +188,16 @@ def load_library(path=None):
         L.fpl_resume_bgzf_bam.argtypes = [C.c_void_p]
         L.fpl_reserve_bam_tail.restype = C.c_int
         L.fpl_reserve_bam_tail.argtypes = [C.c_void_p, C.c_uint64]
+    if hasattr(L, "fpl_process_bgzf_text_async"):  # (found by name too: without them Engine.submit_bgzf_text raises)
+        L.fpl_process_bgzf_text_async.restype = C.c_int
+        L.fpl_process_bgzf_text_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]
+        L.fpl_peek_bgzf_text.restype = C.c_int
+        L.fpl_peek_bgzf_text.argtypes = [C.c_void_p, C.c_void_p]
+        L.fpl_start_bgzf_text.restype = C.c_int
+        L.fpl_start_bgzf_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fpl_wait_bgzf_text.restype = C.c_int
+        L.fpl_wait_bgzf_text.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     if L.fpl_abi_version() != abi.FPL_ABI_VERSION:
         raise FplError("ABI version mismatch")
     if path is None:
@@ -274,18 +285,22 @@ def _b(s):
 class BgzfBatch:
     """One submission of Engine.submit_bgzf.  Batches are collected in the order of submission, each through its own wait()."""
 
+    WINDOW = abi.BAM_WINDOW_DTYPE
+    OK = abi.FPL_BAMW_OK
+    PEEK, START, WAIT = "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam"
+
     def __init__(self, eng, gzip, keep):
         self.eng, self.gzip, self._keep = eng, gzip, keep
         self._outs = None
 
-    @staticmethod
-    def _info(win):
-        return {k: int(win[0][k]) for k, _ in abi.BAM_WINDOW_DTYPE}
+    @classmethod
+    def _info(cls, win):
+        return {k: int(win[0][k]) for k, _ in cls.WINDOW}
 
     def peek(self):
-        """fpl_peek_bgzf_bam: the walk's header as a dict (this must be the oldest BGZF batch that is not started)"""
-        win = np.zeros(1, np.dtype(abi.BAM_WINDOW_DTYPE))
-        self.eng._check(self.eng.L.fpl_peek_bgzf_bam(self.eng.h, win.ctypes.data), "fpl_peek_bgzf_bam")
+        """fpl_peek_bgzf_bam (fpl_peek_bgzf_text): the walk's header as a dict (this must be the oldest BGZF batch that is not started)"""
+        win = np.zeros(1, np.dtype(self.WINDOW))
+        self.eng._check(getattr(self.eng.L, self.PEEK)(self.eng.h, win.ctypes.data), self.PEEK)
         return self._info(win)
 
     def wait(self, want_reads=True, seq_out=None, qual_out=None):
@@ -300,23 +315,23 @@ class BgzfBatch:
             raise FplError("BgzfBatch.wait: seq_out and qual_out go together")
         if want_reads and self._outs is None:
             h = self.peek()
-            if h["status"] == abi.FPL_BAMW_OK and h["n_reads"]:
+            if h["status"] == self.OK and h["n_reads"]:
                 if seq_out is not None:
                     if min(len(seq_out), len(qual_out)) < h["n_bases"] or seq_out.dtype != np.uint8 or qual_out.dtype != np.uint8:
                         raise FplError("BgzfBatch.wait: seq_out / qual_out are uint8 arrays of at least n_bases = %d bytes" % h["n_bases"])
                     self._outs = (seq_out, qual_out)
                 else:
                     self._outs = (e.pinned_array(h["n_bases"] + 1, keep=False), e.pinned_array(h["n_bases"] + 1, keep=False))
-                e._check(e.L.fpl_start_bgzf_bam(e.h, self._outs[0].ctypes.data, self._outs[1].ctypes.data), "fpl_start_bgzf_bam")
-        win = np.zeros(1, np.dtype(abi.BAM_WINDOW_DTYPE))
+                e._check(getattr(e.L, self.START)(e.h, self._outs[0].ctypes.data, self._outs[1].ctypes.data), self.START)
+        win = np.zeros(1, np.dtype(self.WINDOW))
         rp, npp, op, gp, gl = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(0)
-        e._check(e.L.fpl_wait_bgzf_bam(e.h, win.ctypes.data, C.byref(rp), C.byref(npp), C.byref(op), C.byref(gp) if self.gzip else None,
-                                       C.byref(gl) if self.gzip else None), "fpl_wait_bgzf_bam")
+        e._check(getattr(e.L, self.WAIT)(e.h, win.ctypes.data, C.byref(rp), C.byref(npp), C.byref(op), C.byref(gp) if self.gzip else None,
+                                         C.byref(gl) if self.gzip else None), self.WAIT)
         self._keep = None
         h = self._info(win)
         member = (C.string_at(gp.value, gl.value) if gl.value else b"") if self.gzip else None
         n = h["n_reads"]
-        if h["status"] != abi.FPL_BAMW_OK or n == 0:
+        if h["status"] != self.OK or n == 0:
             return h, np.zeros(0, dtype=abi.RESULT_DTYPE), [], None, None, member
         res = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_uint8)), shape=(n * 36,)).view(abi.RESULT_DTYPE).copy()
         off = np.ctypeslib.as_array(C.cast(op, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
@@ -326,6 +341,15 @@ class BgzfBatch:
         if self._outs is not None:
             seq, qual = self._outs[0][:h["n_bases"]], self._outs[1][:h["n_bases"]]
         return h, res, names, seq, qual, member
+
+
+class BgzfTextBatch(BgzfBatch):
+    """One submission of Engine.submit_bgzf_text: BgzfBatch's peek() and wait() over the calls and the header of the BGZF text
+    path.  wait() -> (header dict of abi.TEXT_WINDOW_DTYPE, records, names -- every read's whole first line, '@' included --,
+    bases, qualities, gzip member); bases and qualities are a CSR pair, read i at the running sum of the reads' lengths."""
+    WINDOW = abi.TEXT_WINDOW_DTYPE
+    OK = abi.FPL_TXTW_OK
+    PEEK, START, WAIT = "fpl_peek_bgzf_text", "fpl_start_bgzf_text", "fpl_wait_bgzf_text"
 
 
 class Engine:
@@ -453,6 +477,22 @@ class Engine:
         self._check(self.L.fpl_process_bgzf_bam_async(self.h, comp.ctypes.data if len(comp) else None, len(comp),
                                                       blk.ctypes.data if len(blk) else None, len(blk), int(skip)), "fpl_process_bgzf_bam_async")
         return BgzfBatch(self, bool(gzip), (comp, blk))
+
+    def submit_bgzf_text(self, comp, blocks, gzip=False):
+        """fpl_process_bgzf_text_async: the payloads of a BGZF-compressed FASTQ's blocks and their descriptors, as for submit_bgzf
+        (fastplong_amd.bgzf.blocks cuts any BGZF file into them).  Inflate, the cut at a record's end, the parse and the per-read
+        kernels all run on the device -> a BgzfTextBatch with peek() and wait().  gzip=True: the passing reads also come back as a
+        gzip member.  The tail between two submissions is bam_tail() / set_bam_tail() / resume_bgzf() / reserve_bam_tail()'s."""
+        if not hasattr(self.L, "fpl_process_bgzf_text_async"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_process_bgzf_text_async")
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        blk = np.array(blocks, dtype=np.dtype(abi.BGZF_BLOCK_DTYPE), copy=True, ndmin=1) if len(blocks) else np.zeros(0, np.dtype(abi.BGZF_BLOCK_DTYPE))
+        if gzip or getattr(self, "_gz_on", False):  # (the switch is the context's: touched only when it has to change)
+            self._check(self.L.fpl_set_text_gzip(self.h, int(bool(gzip))), "fpl_set_text_gzip")
+            self._gz_on = bool(gzip)
+        self._check(self.L.fpl_process_bgzf_text_async(self.h, comp.ctypes.data if len(comp) else None, len(comp),
+                                                       blk.ctypes.data if len(blk) else None, len(blk)), "fpl_process_bgzf_text_async")
+        return BgzfTextBatch(self, bool(gzip), (comp, blk))
 
     def bam_tail(self):
         """fpl_bam_tail_get: the bytes behind the last whole record of the BGZF submissions so far"""

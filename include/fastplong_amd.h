@@ -526,7 +526,9 @@ void fpl_inflater_destroy(fpl_inflater* inf);
  *                      A refused submission counts nothing, leaves the tail exactly as it was, and sets a flag in device memory
  *                      that the walks of the submissions already queued behind it read: they refuse with FPL_BAMW_CHAIN.
  *
- * Recovery (all three: FPL_ERR_STATE while a batch of this kind is in flight):
+ * Recovery (shared with the BGZF text path below, whose submissions keep their tail in the same place; all four calls:
+ * FPL_ERR_STATE while a batch of either kind is in flight.  A context's tail belongs to the kind that submitted last, and this
+ * kind's submission is FPL_ERR_STATE while the context holds a BGZF text tail as far as the host knows):
  *   fpl_bam_tail_get   the tail's bytes into buf (cap bytes; *len gets the length, FPL_ERR_ARG with *len set when cap is short).
  *   fpl_bam_tail_set   replaces the tail and clears the flag; len 0 is a new file (skip is allowed again, record indices restart).
  *   fpl_resume_bgzf_bam  clears the flag and keeps the tail (an empty one allows skip again): the refused blocks are submitted
@@ -571,6 +573,94 @@ int fpl_bam_tail_get(fpl_ctx* ctx, uint8_t* buf, uint64_t cap, uint64_t* len);
 int fpl_bam_tail_set(fpl_ctx* ctx, const uint8_t* bytes, uint64_t len);
 int fpl_resume_bgzf_bam(fpl_ctx* ctx);
 int fpl_reserve_bam_tail(fpl_ctx* ctx, uint64_t bytes);
+
+/*
+ * BGZF-compressed FASTQ in, records out: the blocks of a .fastq.gz that bgzip (or `samtools fastq | bgzip`) wrote are inflated, cut
+ * at a record's end, parsed and run on the device, the inflated text never leaving it (csrc/bgzf_inflate.h -> csrc/text_walk.h ->
+ * the per-read kernels, and with fpl_set_text_gzip on, the text forms of the gzip kernels).  FPL_ABI_VERSION stays 10: found by
+ * symbol lookup; a library without these calls is a valid v10 library, and the caller then inflates on the host and takes
+ * fpl_process_text_async.
+ *
+ * A window of blocks rarely ends at a record's end.  The bytes start at a record (the file's start, or the tail), so with L line
+ * breaks in [tail | inflated bytes] the submission holds L / 4 records, and the bytes behind line break 4 (L / 4) - 1 are the new
+ * TAIL.  The tail, its capacity, the refusal flag and the four recovery calls are those of the BGZF-BAM path above
+ * (fpl_bam_tail_get, fpl_bam_tail_set, fpl_resume_bgzf_bam, fpl_reserve_bam_tail): a context's tail belongs to the kind that
+ * submitted last, and submitting the OTHER kind while the context is not fresh -- its tail empty as far as the host knows, the
+ * condition that allows fpl_process_bgzf_bam_async's skip -- is FPL_ERR_STATE.  The recovery calls are FPL_ERR_STATE while a
+ * batch of either kind is in flight.
+ *
+ *   fpl_process_bgzf_text_async  the arguments of fpl_process_bgzf_bam_async without skip: payloads and descriptors in order and
+ *                      without gaps, ranges checked on the calling thread (FPL_ERR_ARG, nothing enqueued); the tail capacity plus
+ *                      the inflated bytes is at most 0xFFFFFFF0 (line positions are 32 bits).  Takes one of the FPL_MAX_IN_FLIGHT
+ *                      slots, FIFO.  A submission made while fpl_set_text_gzip is on is a gzip batch.  Contexts with
+ *                      break_enabled / mask_enabled: FPL_ERR_STATE, as for text.  comp and blocks must stay valid until the batch
+ *                      has been peeked at or waited for.
+ *   fpl_peek_bgzf_text waits for the header of the oldest such batch that is not started, and fills *out; nothing is counted yet.
+ *   fpl_start_bgzf_text  enqueues the per-read kernels of that batch.  seq_out, qual_out: page-locked arrays of n_bases bytes (the
+ *                      header's) that get the bases and qualities as a CSR pair (read i at the running sum of the lengths in
+ *                      results), or both NULL: the arrays stay on the device.  One NULL: FPL_ERR_ARG.
+ *   fpl_wait_bgzf_text the oldest batch in flight, which must be of this kind (FPL_ERR_STATE otherwise, nothing touched -- and
+ *                      every other wait is FPL_ERR_STATE for a batch of this kind).  Starts it with NULL arrays if it was not
+ *                      started.  *out is the header; for status FPL_TXTW_OK *results are the n_reads records, *names the name_bytes
+ *                      bytes of all names -- every read's whole first line, '@' included, without its line break ("\n" or
+ *                      "\r\n"), nothing between them -- and *name_off n_reads + 1 offsets into them; library memory, valid until
+ *                      the next submission that takes this batch's slot.  gz, gz_len (may be NULL, together): the member of
+ *                      fpl_wait_text_gz when the batch is a gzip batch.
+ *
+ *   status             FPL_TXTW_OK: taken whole.  FPL_TXTW_BLOCK: a block k_bgzf_inflate did not vouch for, bad_index is the
+ *                      first.  FPL_TXTW_IRREGULAR: text in front of the cut that fpl_process_text_async would call irregular -- a
+ *                      blank line, a '\r' that is not followed by '\n', a record that fails the '@' / '+' / equal-lengths checks;
+ *                      bad_index is the first failing record's index in the file (from the first submission of the file on), ~0
+ *                      when only the structure failed, and bad_pos the offset in [the tail | this submission's inflated bytes]
+ *                      of that record or of the '\r', whichever comes first.  (A '\r' that is the last byte of a submission is
+ *                      judged with the next one, when the byte behind it is there.)
+ *                      FPL_TXTW_STRAND: a third line longer than "+" once its "\r" is taken off.  Such a line repeats the name;
+ *                      the names this path gives back cannot carry it, and the gzip member writes the line as it stands, so a
+ *                      file with such lines takes the host path.  bad_index / bad_pos: that record.
+ *                      FPL_TXTW_TAIL_ROOM: the new tail (tail_bytes) exceeds the context's tail capacity.
+ *                      FPL_TXTW_TOO_MANY: more records than one per 64 bytes of [tail room | inflated bytes] and 16, or names that
+ *                      take more than a quarter of that and 1 MiB.
+ *                      FPL_TXTW_CHAIN: an earlier submission was refused.
+ *                      A refused submission counts nothing, leaves the tail exactly as it was, and sets the flag in device memory
+ *                      that the submissions already queued behind it read: they refuse with FPL_TXTW_CHAIN.
+ *   records_seen       the records of the file in the submissions accepted so far, this one included.
+ *
+ * A refused stretch goes through the host path without losing a record:
+ *     fpl_bam_tail_get -> T;  inflate the refused blocks on the host -> B;  parse T + B with the host's reader, which keeps the
+ *     bytes behind the last whole record -> R;  the records through fpl_process_batch_async;  fpl_bam_tail_set(R);  go on with
+ *     the blocks behind the refused ones.   For FPL_TXTW_TAIL_ROOM: fpl_reserve_bam_tail(tail_bytes), fpl_resume_bgzf_bam, and
+ *     the refused blocks (and those refused with CHAIN behind them) again.
+ * End of input: a file's last line break makes the last tail empty.  A file without one leaves its last record in the tail:
+ *     fpl_bam_tail_get -> the record's bytes, through the host's reader and fpl_process_batch_async -- today's treatment of a
+ *     chunk without a final line break.  fpl_bam_tail_set(ctx, NULL, 0) then starts a new file.
+ */
+typedef struct fpl_text_window { /* 64 bytes */
+    uint32_t status;
+    uint32_t n_reads;
+    uint64_t n_bases;
+    uint32_t max_read_len;
+    uint32_t n_lines;      /* line breaks in [tail | inflated bytes] */
+    uint64_t name_bytes;
+    uint64_t records_seen;
+    uint32_t tail_bytes;
+    uint32_t reserved;
+    uint64_t bad_index;
+    uint64_t bad_pos;
+} fpl_text_window;
+enum {
+    FPL_TXTW_OK = 0,
+    FPL_TXTW_BLOCK = 1,
+    FPL_TXTW_IRREGULAR = 2,
+    FPL_TXTW_TAIL_ROOM = 3,
+    FPL_TXTW_TOO_MANY = 4,
+    FPL_TXTW_CHAIN = 5,
+    FPL_TXTW_STRAND = 6
+};
+int fpl_process_bgzf_text_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_bytes, const fpl_bgzf_block* blocks, uint32_t n_blocks);
+int fpl_peek_bgzf_text(fpl_ctx* ctx, fpl_text_window* out);
+int fpl_start_bgzf_text(fpl_ctx* ctx, uint8_t* seq_out, uint8_t* qual_out);
+int fpl_wait_bgzf_text(fpl_ctx* ctx, fpl_text_window* out, const fpl_read_result** results, const uint8_t** names, const uint64_t** name_off,
+                       const uint8_t** gz, uint64_t* gz_len);
 
 /*
  * ONE LONG deflate stream -- the payload of an ordinary one-member .gz -- inflated on the device, a window of compressed bytes per

@@ -307,6 +307,13 @@ int fpl_bam_tail_get(fpl_ctx*, uint8_t*, uint64_t, uint64_t* len) {
 int fpl_bam_tail_set(fpl_ctx*, const uint8_t*, uint64_t) { return FPL_ERR_NO_DEVICE; }
 int fpl_resume_bgzf_bam(fpl_ctx*) { return FPL_ERR_NO_DEVICE; }
 int fpl_reserve_bam_tail(fpl_ctx*, uint64_t) { return FPL_ERR_NO_DEVICE; }
+/* (the resident BGZF text path is the device's inflate and cut: the null device refuses, and a host takes fpl_process_text_async) */
+int fpl_process_bgzf_text_async(fpl_ctx*, const uint8_t*, uint64_t, const fpl_bgzf_block*, uint32_t) { return FPL_ERR_NO_DEVICE; }
+int fpl_peek_bgzf_text(fpl_ctx*, fpl_text_window*) { return FPL_ERR_STATE; }
+int fpl_start_bgzf_text(fpl_ctx*, uint8_t*, uint8_t*) { return FPL_ERR_STATE; }
+int fpl_wait_bgzf_text(fpl_ctx*, fpl_text_window*, const fpl_read_result**, const uint8_t**, const uint64_t**, const uint8_t**, uint64_t*) {
+    return FPL_ERR_STATE;
+}
 /* (the emitted batch lives in device memory: the null device has none) */
 int fpl_emit_batch_device(fpl_ctx*, const uint8_t*, const uint8_t*, const uint64_t*, uint32_t, const fpl_read_result*, uint8_t*, uint8_t*, uint64_t,
                           uint64_t*, uint32_t, uint32_t*, uint8_t*, fpl_emit_info*, void*) {
