@@ -26,6 +26,9 @@ FPL_ERR_ADAPTER = -4
 FPL_ERR_CAPACITY = -5
 FPL_ERR_STATE = -6
 
+FPL_GZIP_MEMBER = 0  # fpl_set_gzip_framing
+FPL_GZIP_BGZF = 1
+
 FPL_TEXT_OK = 0
 FPL_TEXT_IRREGULAR = 1
 FPL_TEXT_TOO_MANY = 2

@@ -8,6 +8,10 @@ import numpy as np
 from . import abi
 
 
+# the empty block that ends every BGZF file (SAM specification, 4.1.2)
+EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
 class BgzfError(ValueError):
     pass
 

@@ -29,6 +29,14 @@
  *   k_gz_compact  a workgroup per deflate block: its bytes to their place in the member
  *
  * Worst case: gz_len <= GZ_MEMBER_EXTRA + total + GZ_SLACK * n_blocks, n_blocks <= total / GZ_B + 1 + 2 * (long fragments).
+ *
+ * The BGZF form (fpl_set_gzip_framing): the same layout and compose; the text in stripes of GZ_STRIPE bytes, one BGZF block each
+ *   k_gz_block_bgzf   k_gz_block's body with two distance code lengths in the dynamic header (a complete set) and the block's CRC
+ *                     remainder shifted to the end of its stripe
+ *   k_gz_finish_bgzf  one block: the same prefix sums, every block placed behind the frames in front of it; the batch's CRC-32
+ *   k_gz_frame        a thread per stripe: header with BSIZE, final empty block, CRC-32 and ISIZE of the stripe
+ *   k_gz_compact      unchanged
+ * Worst case: gz_len <= total + GZ_SLACK * n_blocks + GZ_BGZF_EXTRA * ceil(total / GZ_STRIPE) (beside GZ_STRIPE below).
  */
 #ifndef FPL_GZ_EMIT_H
 #define FPL_GZ_EMIT_H
@@ -45,12 +53,24 @@ constexpr int GZ_THREADS = 256;
 constexpr u32 GZ_STRETCH = GZ_B / GZ_THREADS; /* symbols a thread packs */
 constexpr u32 GZ_SLACK = 5;                   /* a stored block's header: the most a block grows by */
 constexpr u32 GZ_MEMBER_EXTRA = 10 + 5 + 8;   /* gzip header, final empty block, CRC-32 + ISIZE */
+/* The BGZF form (fpl_set_gzip_framing): BGZF block k of a batch holds bytes [k * GZ_STRIPE, min((k + 1) * GZ_STRIPE, total)) of the
+   composed text.  Every multiple of GZ_B starts a deflate block, so a stripe is a whole number of the deflate blocks the layout
+   cuts, whatever their compressed sizes.  Worst case of one BGZF block: a stripe holds at most 3 + 2 * ceil(49 152 / 2 050) + 1 =
+   52 deflate blocks (its three multiples of GZ_B, two forced starts per fragment of at least GZ_L - 1 bases -- such a fragment
+   writes at least 2 * (GZ_L - 1) + 4 = 2 050 bytes --, one for what is left of a fragment that began in the stripe before), each
+   grows by at most GZ_SLACK, so the block stays below 49 152 + 5 * 53 + 31 = 49 448 bytes: far inside BGZF's 65 536. */
+constexpr u32 GZ_STRIPE = 3 * GZ_B;
+constexpr u32 GZ_BGZF_HEAD = 18;                       /* gzip header with the BC extra field */
+constexpr u32 GZ_BGZF_EXTRA = GZ_BGZF_HEAD + 5 + 8;    /* header, final empty block, CRC-32 + ISIZE: per BGZF block */
+constexpr u32 GZ_BGZF_MAX = 65536;
+static_assert(GZ_STRIPE % GZ_B == 0 && GZ_STRIPE + GZ_SLACK * (3 + 2 * ((GZ_STRIPE + 2 * GZ_L + 1) / (2 * GZ_L + 2)) + 2) + GZ_BGZF_EXTRA <= GZ_BGZF_MAX,
+              "a stripe's worst case must fit a BGZF block");
 constexpr u32 GZ_CRC_POLY = 0xEDB88320u;
 constexpr int GZ_NSYM = 257; /* 256 literals + end-of-block */
 
 struct GzHeader {
     u64 total;    /* bytes of the composed text */
-    u64 gz_len;   /* bytes of the member (0 when total is 0) */
+    u64 gz_len;   /* bytes of the member, or of the batch's BGZF blocks together (0 when total is 0) */
     u32 n_blocks; /* deflate blocks with data */
     u32 status;   /* bit 0: more blocks than the caller's arrays hold (nothing usable) */
     u32 crc;      /* CRC-32 of the composed text */
@@ -59,6 +79,11 @@ struct GzHeader {
 
 /* most deflate blocks a chunk of text_bytes bytes and n_rec records can be cut into (both fragments of a split read repeat the
    name and the '+' line, and each may start two blocks) */
+/* the output bound of either form: what the buffers are sized by */
+inline u64 gz_bgzf_blocks(u64 total) { return (total + GZ_STRIPE - 1) / GZ_STRIPE; }
+inline u64 gz_out_bound(u64 total, u64 n_blocks, bool bgzf) {
+    return total + (u64)GZ_SLACK * n_blocks + (bgzf ? (u64)GZ_BGZF_EXTRA * gz_bgzf_blocks(total) : (u64)GZ_MEMBER_EXTRA);
+}
 inline u64 gz_total_bound(u64 text_bytes, u64 n_rec) { return 2 * text_bytes + 46 * n_rec; }
 inline u64 gz_blocks_bound(u64 text_bytes, u64 n_rec) { return gz_total_bound(text_bytes, n_rec) / GZ_B + 2 + 4 * n_rec; }
 /* the same for a BAM batch of n_bases bases: a fragment is at most its read, and writes a name line of at most 1 + 254 + 23 bytes,
@@ -83,6 +108,11 @@ __device__ __forceinline__ u32 gz_xpow8(u64 n) { /* x^(8 n) mod P */
         n >>= 1;
     }
     return r;
+}
+/* where the stripe of byte `at` ends: the next multiple of GZ_STRIPE, or the end of the text */
+__device__ __forceinline__ u64 gz_stripe_end(u64 at, u64 total) {
+    const u64 e = (at / GZ_STRIPE + 1) * (u64)GZ_STRIPE;
+    return e < total ? e : total;
 }
 __device__ __forceinline__ u32 gz_crc_table_entry(u32 i) {
     u32 c = i;
@@ -478,10 +508,12 @@ __device__ __forceinline__ u32 gz_rev(u32 code, u32 len) { return len ? brev32(c
 constexpr u32 GZ_OUT_WORDS = (GZ_B + GZ_SLACK + 3) / 4 + 2;
 
 /* a workgroup per deflate block.  tmp: block b's bytes at blk_start[b] + GZ_SLACK * b, blk_size[b] of them;
-   blk_crc[b]: the block's share of the member's raw CRC remainder */
-__global__ void __launch_bounds__(GZ_THREADS)
-k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const GzHeader* __restrict__ hdr, u8* __restrict__ tmp,
-           u32* __restrict__ blk_size, u32* __restrict__ blk_crc) {
+   blk_crc[b]: the block's share of the member's raw CRC remainder.  BGZF: the share of its BGZF block's remainder (the block's
+   bytes shifted to the end of its stripe), and a dynamic header that declares TWO distance codes of length 1 -- a complete set,
+   which every inflater takes; the member form's single code is what k_bgzf_inflate refuses. */
+template <bool BGZF>
+__device__ __forceinline__ void gz_block_body(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const GzHeader* __restrict__ hdr,
+                                              u8* __restrict__ tmp, u32* __restrict__ blk_size, u32* __restrict__ blk_crc) {
     __shared__ u32 in_w[GZ_B / 4 + 4];
     __shared__ u32 out_w[GZ_OUT_WORDS];
     __shared__ u32 hist[GZ_NSYM + 3];
@@ -535,7 +567,9 @@ k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const
         if (tid == 64) { /* (beside thread 0's serial work below) */
             u32 c = 0;
             for (int k = 0; k < GZ_THREADS / 64; k++) c ^= wsum[k];
-            blk_crc[b] = gz_mulmod(c, gz_xpow8(total - (s0 + n)));
+            u64 end = total;
+            if (BGZF) end = gz_stripe_end(s0, total);
+            blk_crc[b] = gz_mulmod(c, gz_xpow8(end - (s0 + n)));
         }
         gz_code_lengths(hist, GZ_NSYM, 15, len, &scratch);
         /* canonical codes: symbols of one length in symbol order */
@@ -556,11 +590,11 @@ k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const
             code[s] = (u16)(l ? gz_rev(scratch.cnt[l] + rank, l) : 0u);
         }
         __syncthreads();
-        /* the header: run-length symbols over the 257 literal lengths and the one distance length (1) */
+        /* the header: run-length symbols over the 257 literal lengths and the distance lengths (one 1; BGZF: two) */
         if (tid == 0) {
             u32 m = 0;
             for (int i = 0; i < 19; i++) cl_freq[i] = 0;
-            for (u32 i = 0; i < GZ_NSYM + 1;) {
+            for (u32 i = 0; i < GZ_NSYM + (BGZF ? 2u : 1u);) {
                 const u32 v = i < GZ_NSYM ? len[i] : 1u;
                 if (v != 0) {
                     cl_sym[m] = (u8)v, cl_extra[m] = 0, m++, i++;
@@ -610,7 +644,7 @@ k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const
             bw.put(0, 1);  /* BFINAL */
             bw.put(2, 2);  /* BTYPE: dynamic */
             bw.put(0, 5);  /* HLIT: 257 codes */
-            bw.put(0, 5);  /* HDIST: 1 code */
+            bw.put(BGZF ? 1 : 0, 5);  /* HDIST: 1 code; BGZF: 2 */
             bw.put(hclen - 4, 4);
             for (u32 i = 0; i < hclen; i++) bw.put(cl_len[order[i]], 3);
             const u32 m = n_cl;
@@ -685,6 +719,16 @@ k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const
         if (tid == 0) blk_size[b] = size;
     }
 }
+__global__ void __launch_bounds__(GZ_THREADS)
+k_gz_block(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const GzHeader* __restrict__ hdr, u8* __restrict__ tmp,
+           u32* __restrict__ blk_size, u32* __restrict__ blk_crc) {
+    gz_block_body<false>(comp, blk_start, hdr, tmp, blk_size, blk_crc);
+}
+__global__ void __launch_bounds__(GZ_THREADS)
+k_gz_block_bgzf(const u8* __restrict__ comp, const u64* __restrict__ blk_start, const GzHeader* __restrict__ hdr, u8* __restrict__ tmp,
+                u32* __restrict__ blk_size, u32* __restrict__ blk_crc) {
+    gz_block_body<true>(comp, blk_start, hdr, tmp, blk_size, blk_crc);
+}
 
 /* one block: blk_off[b] = bytes of the member in front of block b's; header, final block, trailer; hdr->gz_len, hdr->crc */
 __global__ void __launch_bounds__(1024)
@@ -742,6 +786,152 @@ k_gz_finish(const u32* __restrict__ blk_size, const u32* __restrict__ blk_crc, u
     }
 }
 
+/* The BGZF form of the finish.  One block: the running sum of the deflate blocks' sizes as above; a deflate block's place is the
+   sum in front of it plus the frames in front of it and its own stripe's header: blk_off[b] = sum + 18 + 31 * (blk_start[b] /
+   GZ_STRIPE).  hdr->crc stays the CRC-32 of the whole composed text: every block's remainder stands at the end of its stripe
+   (k_gz_block_bgzf) and is shifted on to the end of the text here.  Every thread takes a run of consecutive blocks and
+   carries ONE remainder through it, multiplied by x^(8 * the next stripe's bytes) whenever the run enters the next stripe; at
+   the end of the run what is left to the end of the text is a whole number m of stripes and the last stripe's length, and
+   x^(8 * GZ_STRIPE * 2^j) for the bits j of m comes from a table of 32 entries.  (A gz_xpow8 per block, each a chain of some
+   sixty gz_mulmod, was 22 ms for the 122 000 blocks of a 1 Gbase batch; the table per block still 5.)  hdr->gz_len = the
+   BGZF blocks together. */
+__global__ void __launch_bounds__(1024)
+k_gz_finish_bgzf(const u64* __restrict__ blk_start, const u32* __restrict__ blk_size, const u32* __restrict__ blk_crc,
+                 u64* __restrict__ blk_off, GzHeader* __restrict__ hdr, u64 out_cap) {
+    __shared__ u64 wsum[16];
+    __shared__ u32 wcrc[16];
+    __shared__ u64 carry;
+    __shared__ u32 pw[32], last_pw;
+    const u32 n_blocks = hdr->n_blocks;
+    const u64 total = hdr->total;
+    const u64 n_stripes = (total + GZ_STRIPE - 1) / GZ_STRIPE;
+    if (threadIdx.x == 0) carry = 0;
+    if (threadIdx.x < 32) { /* pw[j] = x^(8 * GZ_STRIPE * 2^j) */
+        u32 r = gz_xpow8(GZ_STRIPE);
+        for (u32 j = 0; j < threadIdx.x; j++) r = gz_mulmod(r, r);
+        pw[threadIdx.x] = r;
+    }
+    if (threadIdx.x == 32) last_pw = n_stripes ? gz_xpow8(total - (n_stripes - 1) * GZ_STRIPE) : 0u; /* x^(8 * the last stripe's bytes) */
+    u32 crc = 0;
+    __syncthreads();
+    {
+        const u32 per = (n_blocks + 1023) / 1024;
+        const u32 b0 = min(n_blocks, threadIdx.x * per), b1 = n_blocks - b0 < per ? n_blocks : b0 + per;
+        u64 cur = b0 < b1 ? blk_start[b0] / GZ_STRIPE : 0u; /* the stripe crc stands at the end of */
+        /* (eight blocks' loads at a time: a lane's run is its own stretch of memory, so a load of one element per lane is 64
+           cache lines, and 240 of them one after the other were most of this kernel's 5 ms on a 1 Gbase batch) */
+        for (u32 i0 = b0; i0 < b1; i0 += 8) {
+            u64 st[8];
+            u32 cr[8];
+#pragma unroll
+            for (u32 k = 0; k < 8; k++) {
+                const u32 i = i0 + k < b1 ? i0 + k : b1 - 1;
+                st[k] = blk_start[i];
+                cr[k] = blk_crc[i];
+            }
+#pragma unroll
+            for (u32 k = 0; k < 8; k++) {
+                if (i0 + k >= b1) break;
+                const u64 stripe = st[k] / GZ_STRIPE;
+                for (; cur < stripe; cur++) /* (every stripe has a block: one step at most) */
+                    crc = crc ? gz_mulmod(crc, cur + 2 == n_stripes ? last_pw : pw[0]) : 0u;
+                crc ^= cr[k];
+            }
+        }
+        if (crc && cur + 1 < n_stripes) { /* (n_stripes <= n_blocks < 2^32: m has at most 32 bits) */
+            u32 f = last_pw;
+            u64 m = n_stripes - 2 - cur;
+            for (int j = 0; m && j < 32; j++, m >>= 1)
+                if (m & 1ull) f = gz_mulmod(f, pw[j]);
+            crc = gz_mulmod(crc, f);
+        }
+    }
+    for (u32 base = 0; base < n_blocks; base += 1024) { /* block-uniform */
+        const u32 i = base + threadIdx.x;
+        u64 v = 0, stripe = 0;
+        if (i < n_blocks) { /* (both loads under one branch: in flight together) */
+            const u32 sz = blk_size[i];
+            const u64 at = blk_start[i];
+            v = sz, stripe = at / GZ_STRIPE;
+        }
+        const u64 incl = gz_scan_incl_u64(v);
+        if (lane_id() == 63) wsum[wave_in_block()] = incl;
+        __syncthreads();
+        u64 run = carry + incl - v;
+        for (int k = 0; k < wave_in_block(); k++) run += wsum[k];
+        if (i < n_blocks) blk_off[i] = run + GZ_BGZF_HEAD + (u64)GZ_BGZF_EXTRA * stripe;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = run + v;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) crc ^= shfl_xor_u32(crc, d);
+    if (lane_id() == 0) wcrc[wave_in_block()] = crc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (total == 0 || hdr->status) {
+            hdr->gz_len = 0;
+            return;
+        }
+        u32 raw = 0;
+        for (int k = 0; k < 16; k++) raw ^= wcrc[k];
+        hdr->crc = raw ^ gz_mulmod(0xFFFFFFFFu, gz_xpow8(total)) ^ 0xFFFFFFFFu;
+        const u64 len = carry + (u64)GZ_BGZF_EXTRA * ((total + GZ_STRIPE - 1) / GZ_STRIPE);
+        hdr->gz_len = len;
+        if (len > out_cap) {
+            hdr->status = 1;
+            hdr->gz_len = 0;
+        }
+    }
+}
+
+/* A thread per stripe, behind k_gz_finish_bgzf: the stripe's deflate blocks are those whose start lies in it (a search in
+   blk_start: the stripe's first byte is a multiple of GZ_B, so it IS a start); their remainders XORed are the raw remainder of
+   the stripe's bytes, the all-ones term of its length makes the CRC-32.  Writes the 18-byte header with BSIZE in front of the
+   stripe's first deflate block and, behind its last, the final empty stored block, CRC-32 and ISIZE.  A block over 65 536 bytes
+   (the bound beside GZ_STRIPE says there is none) is a status, not a file. */
+__global__ void __launch_bounds__(256)
+k_gz_frame(const u64* __restrict__ blk_start, const u32* __restrict__ blk_size, const u32* __restrict__ blk_crc,
+           const u64* __restrict__ blk_off, GzHeader* __restrict__ hdr, u8* __restrict__ out, u64 out_cap) {
+    if (hdr->gz_len == 0) return; /* (nothing to write, or the finish found the output too small) */
+    const u32 n_blocks = hdr->n_blocks;
+    const u64 total = hdr->total;
+    const u64 n_stripes = (total + GZ_STRIPE - 1) / GZ_STRIPE;
+    for (u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x; k < n_stripes; k += (u64)gridDim.x * blockDim.x) {
+        const u64 s = k * GZ_STRIPE, e = gz_stripe_end(s, total);
+        /* first block that starts at or behind s, and at or behind e */
+        u32 lo = 0, hi = n_blocks;
+        while (lo < hi) {
+            const u32 mid = lo + (hi - lo) / 2;
+            if (blk_start[mid] < s) lo = mid + 1;
+            else hi = mid;
+        }
+        const u32 b0 = lo;
+        u32 b1 = b0, raw = 0;
+        while (b1 < n_blocks && blk_start[b1] < e) raw ^= blk_crc[b1++];
+        if (b1 == b0) continue; /* (cannot be: s is a block start) */
+        const u64 begin = blk_off[b0] - GZ_BGZF_HEAD;
+        const u64 tail = blk_off[b1 - 1] + blk_size[b1 - 1];
+        const u64 bytes = tail + 13 - begin;
+        if (bytes > GZ_BGZF_MAX) {
+            atomicOr(&hdr->status, 2u);
+            continue;
+        }
+        if (tail + 13 > out_cap) continue;
+        const u32 isize = (u32)(e - s);
+        const u32 c = raw ^ gz_mulmod(0xFFFFFFFFu, gz_xpow8(isize)) ^ 0xFFFFFFFFu;
+        const u8 head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+        u8* h = out + begin;
+        for (int i = 0; i < 16; i++) h[i] = head[i];
+        h[16] = (u8)((bytes - 1) & 0xFF), h[17] = (u8)((bytes - 1) >> 8);
+        u8* t = out + tail;
+        t[0] = 1, t[1] = 0, t[2] = 0, t[3] = 0xff, t[4] = 0xff; /* BFINAL, stored, 0 bytes */
+        for (int i = 0; i < 4; i++) t[5 + i] = (u8)(c >> (8 * i));
+        for (int i = 0; i < 4; i++) t[9 + i] = (u8)(isize >> (8 * i));
+    }
+}
+
+/* (either form: blk_off says where a block's bytes go) */
 __global__ void __launch_bounds__(GZ_THREADS)
 k_gz_compact(const u8* __restrict__ tmp, const u64* __restrict__ blk_start, const u32* __restrict__ blk_size,
              const u64* __restrict__ blk_off, const GzHeader* __restrict__ hdr, u8* __restrict__ out, u64 out_cap) {

@@ -73,7 +73,7 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     }
     if (h.total == 0) return FPL_OK;
     const u32 n = sl.n_reads;
-    const uint64_t out_want = GZ_MEMBER_EXTRA + h.total + (uint64_t)GZ_SLACK * h.n_blocks;
+    const uint64_t out_want = gz_out_bound(h.total, h.n_blocks, g.bgzf);
     FPL_HIP(g.d_comp.grow(h.total + 16, 4096));
     FPL_HIP(g.d_tmp.grow(out_want + 16, 4096));
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
@@ -87,10 +87,22 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
                            (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr,
                            g.d_comp.ptr, (u64)h.total);
     const u32 grid = std::max<u32>(1u, std::min<u32>(h.n_blocks, 8u * ctx->n_cu));
-    hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_comp.ptr, (const u64*)g.d_blk_start.ptr,
-                       (const GzHeader*)g.d_hdr.ptr, g.d_tmp.ptr, g.d_blk_size.ptr, g.d_blk_crc.ptr);
-    hipLaunchKernelGGL(k_gz_finish, dim3(1), dim3(1024), 0, st, (const u32*)g.d_blk_size.ptr, (const u32*)g.d_blk_crc.ptr,
-                       (u64*)g.d_blk_off.ptr, g.d_hdr.ptr, g.d_out.ptr, (u64)out_want);
+    if (g.bgzf) {
+        /* the BGZF form: the same blocks with a complete distance code, placed behind their stripes' headers, then the frames */
+        const u32 n_stripes = (u32)gz_bgzf_blocks(h.total);
+        hipLaunchKernelGGL(k_gz_block_bgzf, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_comp.ptr, (const u64*)g.d_blk_start.ptr,
+                           (const GzHeader*)g.d_hdr.ptr, g.d_tmp.ptr, g.d_blk_size.ptr, g.d_blk_crc.ptr);
+        hipLaunchKernelGGL(k_gz_finish_bgzf, dim3(1), dim3(1024), 0, st, (const u64*)g.d_blk_start.ptr, (const u32*)g.d_blk_size.ptr,
+                           (const u32*)g.d_blk_crc.ptr, (u64*)g.d_blk_off.ptr, g.d_hdr.ptr, (u64)out_want);
+        hipLaunchKernelGGL(k_gz_frame, dim3((n_stripes + 255) / 256), dim3(256), 0, st, (const u64*)g.d_blk_start.ptr,
+                           (const u32*)g.d_blk_size.ptr, (const u32*)g.d_blk_crc.ptr, (const u64*)g.d_blk_off.ptr, g.d_hdr.ptr,
+                           g.d_out.ptr, (u64)out_want);
+    } else {
+        hipLaunchKernelGGL(k_gz_block, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_comp.ptr, (const u64*)g.d_blk_start.ptr,
+                           (const GzHeader*)g.d_hdr.ptr, g.d_tmp.ptr, g.d_blk_size.ptr, g.d_blk_crc.ptr);
+        hipLaunchKernelGGL(k_gz_finish, dim3(1), dim3(1024), 0, st, (const u32*)g.d_blk_size.ptr, (const u32*)g.d_blk_crc.ptr,
+                           (u64*)g.d_blk_off.ptr, g.d_hdr.ptr, g.d_out.ptr, (u64)out_want);
+    }
     hipLaunchKernelGGL(k_gz_compact, dim3(grid), dim3(GZ_THREADS), 0, st, (const u8*)g.d_tmp.ptr, (const u64*)g.d_blk_start.ptr,
                        (const u32*)g.d_blk_size.ptr, (const u64*)g.d_blk_off.ptr, (const GzHeader*)g.d_hdr.ptr, g.d_out.ptr, (u64)out_want);
     FPL_HIP(hipGetLastError());
@@ -100,7 +112,7 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(hipEventSynchronize(g.ev));
     const GzHeader h2 = *g.h_hdr.ptr;
     if (h2.status || h2.gz_len == 0 || h2.gz_len > out_want) {
-        ctx->err = "gzip member: the kernels report a size outside the bound";
+        ctx->err = g.bgzf ? "BGZF blocks: the kernels report a size outside the bound" : "gzip member: the kernels report a size outside the bound";
         return FPL_ERR_STATE;
     }
     /* (the kernels are done: the member goes back on the copy stream, beside the next batch's kernels) */
@@ -167,6 +179,7 @@ static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = kind;
     sl.gz = gz;
+    sl.gzip.bgzf = ctx->gzip_bgzf; /* (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
     sl.n_reads = 0;
     sl.user_results = nullptr;
     sl.rc = FPL_OK;

@@ -112,6 +112,12 @@ int fpl_set_text_gzip(fpl_ctx* ctx, int on) {
     return FPL_OK;
 }
 
+int fpl_set_gzip_framing(fpl_ctx* ctx, int framing) {
+    if (!ctx || (framing != FPL_GZIP_MEMBER && framing != FPL_GZIP_BGZF)) return FPL_ERR_ARG;
+    ctx->gzip_bgzf = framing == FPL_GZIP_BGZF; /* (read by slot_begin: the next submission's slot) */
+    return FPL_OK;
+}
+
 static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
                      const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;

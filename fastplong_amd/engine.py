@@ -25,7 +25,7 @@ EXPORTS = [
     "fpl_count_end_kmers", "fpl_pick_adapter", "fpl_rccl_library", "fpl_comm_init", "fpl_get_batch_forms", "fpl_assume_inputs_ready",
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
-    "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz",
+    "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
@@ -155,6 +155,9 @@ def load_library(path=None):
         L.fpl_set_bam_gzip.argtypes = [C.c_void_p, C.c_int]
         L.fpl_wait_bam_gz.restype = C.c_int
         L.fpl_wait_bam_gz.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    if hasattr(L, "fpl_set_gzip_framing"):  # (found by name: without it Engine.set_gzip_framing raises)
+        L.fpl_set_gzip_framing.restype = C.c_int
+        L.fpl_set_gzip_framing.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
         L.fpl_inflater_create.restype = C.c_void_p
         L.fpl_inflater_create.argtypes = [C.c_int32]
@@ -714,6 +717,13 @@ class Engine:
         out = (C.c_uint64 * 6)()
         self._check(self.L.fpl_get_batch_forms(self.h, out), "fpl_get_batch_forms")
         return dict(batches=int(out[0]), reads=int(out[1]), trim_batched=int(out[2]), stats_sorted=int(out[3]), largest=int(out[4]), trims_ahead=int(out[5]))
+
+    def set_gzip_framing(self, bgzf):
+        """fpl_set_gzip_framing: the bytes of the gzip batches submitted from now on are BGZF blocks (True; fastplong_amd.bgzf.blocks
+        cuts them, bgzf.EOF ends a file of them) or one gzip member per batch (False, the default)"""
+        if not hasattr(self.L, "fpl_set_gzip_framing"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_gzip_framing")
+        self._check(self.L.fpl_set_gzip_framing(self.h, abi.FPL_GZIP_BGZF if bgzf else abi.FPL_GZIP_MEMBER), "fpl_set_gzip_framing")
 
     def gzip_batches(self):
         """batches whose gzip member was made on the device (fpl_get_gzip_batches)"""

@@ -34,6 +34,8 @@ struct DeviceApi {
     WaitTextGzFn wait_text_gz = nullptr;
     SetGzipFn set_bam_gzip = nullptr;
     WaitBamGzFn wait_bam_gz = nullptr;
+    /* --bgzf: the device frames its gzip batches as BGZF blocks (found by name; without it the host frames everything) */
+    SetGzipFn set_gzip_framing = nullptr;
 };
 
 static DeviceApi load_device_api() {
@@ -48,7 +50,18 @@ static DeviceApi load_device_api() {
     a.wait_text_gz = (DeviceApi::WaitTextGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_text_gz");
     a.set_bam_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_gzip");
     a.wait_bam_gz = (DeviceApi::WaitBamGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_bam_gz");
+    a.set_gzip_framing = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_framing");
     return a;
+}
+
+/* BGZF framing on every context or on none */
+static bool frame_on_all(DeviceApi::SetGzipFn set, const vector<fpl_ctx*>& ctxs) {
+    bool on = set != nullptr;
+    for (size_t d = 0; on && d < ctxs.size(); d++)
+        if (set(ctxs[d], FPL_GZIP_BGZF) != FPL_OK) on = false;
+    if (!on)
+        for (size_t d = 0; set && d < ctxs.size(); d++) (void)set(ctxs[d], FPL_GZIP_MEMBER);
+    return on;
 }
 
 /* a gzip form on every context or on none: one context that refuses switches all of them back off (`have_wait`: the wait

@@ -80,7 +80,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""},
 };
 
 struct Args {
@@ -169,6 +169,7 @@ struct Options {
     long chunkMb = 0;
     int readerThreads = 0, compression = 0;
     bool gzStream = false, deviceParse = false, hostParse = false, hostGzip = false, deviceGzip = false, deviceInflate = false;
+    bool bgzf = false; /* --bgzf: every .gz this run writes is BGZF blocks plus the EOF block */
     string command; /* src/main.cpp:252-256 */
     time_t t1 = 0;
 };
@@ -324,6 +325,9 @@ static Options parse_options(int argc, char** argv) {
     p.verbose = cmd.exist("verbose");
     p.gzStream = cmd.exist("gz_stream"), p.deviceParse = cmd.exist("device_parse"), p.hostParse = cmd.exist("host_parse");
     p.hostGzip = cmd.exist("host_gzip"), p.deviceGzip = cmd.exist("device_gzip"), p.deviceInflate = cmd.exist("device_inflate");
+    p.bgzf = cmd.exist("bgzf");
+    if (p.bgzf && !((ends_with_gz(p.out) && !p.toStdout) || (!p.splitEnabled && ends_with_gz(p.failedOut))))
+        error_exit("--bgzf needs an output whose name ends in .gz (--out, --failed_out or the --split files)");
 
     stringstream ss; /* src/main.cpp:252-256 */
     for (int i = 0; i < argc; i++) ss << argv[i] << " ";

@@ -15,6 +15,7 @@
 struct OutFile {
     FILE* f = nullptr;
     bool gz = false;
+    bool bgzf = false; /* --bgzf: the .gz is BGZF blocks, ended by the EOF block */
     bool wrote = false;
     /* FPLH_PARALLEL_WRITE (measurement hook): the pieces of a batch written side by side at their offsets (pwrite from
        the worker pool; nothing goes through the FILE's buffer then).  Measured on the GPU box into tmpfs: no gain -- one
@@ -25,10 +26,11 @@ struct OutFile {
     uint64_t pos = 0;
     explicit operator bool() const { return f != nullptr; }
 
-    static OutFile open(const string& path) {
+    static OutFile open(const string& path, bool bgzf = false) {
         OutFile o;
         if (path.empty()) return o;
         o.gz = ends_with_gz(path);
+        o.bgzf = o.gz && bgzf;
         o.f = fopen(path.c_str(), "wb");
         if (!o.f) error_exit("Failed to write: " + path);
         struct stat st;
@@ -72,7 +74,12 @@ struct OutFile {
     }
     void close(int gzLevel) {
         if (!f) return;
-        if (gz && !wrote) { /* an empty .gz still has to be a gzip stream */
+        if (bgzf) { /* (a file no read reached is exactly this block) */
+            const string& e = fplh::bgzf_eof();
+            if (positional ? pwrite(fileno(f), e.data(), e.size(), (off_t)pos) != (ssize_t)e.size() /* (the FILE's own position is still 0) */
+                           : fwrite(e.data(), 1, e.size(), f) != e.size())
+                error_exit("write failed");
+        } else if (gz && !wrote) { /* an empty .gz still has to be a gzip stream */
             const string e = fplh::gzip_member(string(), gzLevel);
             if (fwrite(e.data(), 1, e.size(), f) != e.size()) error_exit("write failed");
         }
@@ -84,14 +91,18 @@ struct OutFile {
 struct Outputs {
     OutFile fout, ffail;
     int gzLevel = 4;
+    bool bgzf = false; /* --bgzf: the pieces are framed by bgzf_into */
     fplh::SplitOutput* split = nullptr; /* --split / --split_by_lines: the workers' private writers take the passing reads */
     bool gatherOut = false;             /* --out is written as gather lists over the batches' own arrays (build_gather) */
 
     bool any_gz() const { return (fout && fout.gz) || (ffail && ffail.gz); }
     void gzip_pieces(vector<string>& pieces) const { /* in parallel; pieces stay below 4 GiB (one slice of a batch) */
         const int level = gzLevel;
+        const bool blocks = bgzf;
         fplh::parallel_run((int)pieces.size(), [&](int i) {
-            if (!pieces[i].empty()) fplh::gzip_into(pieces[i], level, pieces[i]);
+            if (pieces[i].empty()) return;
+            if (blocks) fplh::bgzf_into(pieces[i], level, pieces[i]);
+            else fplh::gzip_into(pieces[i], level, pieces[i]);
         });
     }
     void close() {
@@ -104,12 +115,13 @@ static Outputs open_outputs(const Options& opt) {
     Outputs o;
     /* with --split* the reference never calls initOutput (src/seprocessor.cpp:65-67): no single --out file and no
        --failed_out either; the workers' private writers take the passing reads */
-    o.fout = OutFile::open(opt.splitEnabled ? string() : opt.out);
-    o.ffail = OutFile::open(opt.splitEnabled ? string() : opt.failedOut);
-    if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.positional = false;
+    o.bgzf = opt.bgzf;
+    o.fout = OutFile::open(opt.splitEnabled ? string() : opt.out, opt.bgzf);
+    o.ffail = OutFile::open(opt.splitEnabled ? string() : opt.failedOut, opt.bgzf);
+    if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.bgzf = false, o.fout.positional = false;
     o.gzLevel = min(9, max(1, opt.compression));
     if (opt.splitEnabled)
-        o.split = new fplh::SplitOutput(opt.out, opt.splitDigits, opt.workers, opt.splitByLines, opt.splitNumber, opt.splitSize, o.gzLevel);
+        o.split = new fplh::SplitOutput(opt.out, opt.splitDigits, opt.workers, opt.splitByLines, opt.splitNumber, opt.splitSize, o.gzLevel, opt.bgzf);
     /* Plain --out alone that is NOT a regular file -- a pipe into an aligner or a compressor (--stdout, /dev/stdout), /dev/null --
        is written as gather lists over the batches' own arrays (build_gather): nothing is formatted.  Into a regular file the
        one writer thread's copy into the page cache is the bottleneck either way (18 GB: 2.9 s from formatted pieces, 3.6 s

@@ -198,6 +198,7 @@ struct Pipeline {
     const int nGpus;
     bool devGz = false;         /* --out *.gz: text batches come back with their gzip member (fpl_wait_text_gz) */
     bool devBamGz = false;      /* ... BAM-backed batches do (fpl_wait_bam_gz) */
+    bool devBgzf = false;       /* --bgzf: ... and those bytes are BGZF blocks (fpl_set_gzip_framing) */
     bool bamKeepArrays = true;  /* a BAM batch's decoded bases are copied back to the host */
     int nFmt = 1, fmtThreads = 1;
     bool splitThreads = false;  /* --split*: the workers' writers have threads of their own */
@@ -213,6 +214,7 @@ struct Pipeline {
     std::atomic<bool> stopInput{false};  /* a device thread found a malformed record: the reader stops cutting chunks */
     std::atomic<uint64_t> nTextBatches{0}, nTextFallbacks{0}; /* --device_parse: chunks the device parsed / chunks handed back to the host's reader */
     std::atomic<uint64_t> nDevGz{0};
+    std::atomic<uint64_t> nDevBgzf{0}; /* --bgzf: BGZF blocks the device framed */
     std::atomic<int> devEnded{0};
 
     /* ---- written by the reader thread alone (read after it is joined) */
@@ -279,7 +281,10 @@ Pipeline::Pipeline(const Options& opt_, const DeviceApi& api_, const InputFacts&
    so do --failed_out's own file, --split*, --break / --mask (never text batches), --host_parse, --host_gzip.
    A library without the entry points (DeviceApi): the host's deflate, without a word. */
 void Pipeline::enable_device_gzip() {
-    const bool eligible = out.fout && out.fout.gz && !out.split && !opt.fragmentMode && !opt.hostGzip && opt.compression <= 4;
+    bool eligible = out.fout && out.fout.gz && !out.split && !opt.fragmentMode && !opt.hostGzip && opt.compression <= 4;
+    /* --bgzf: under the same conditions the device frames its batches as BGZF blocks; a library without fpl_set_gzip_framing
+       makes members only, so the host deflates and frames everything, without a word */
+    if (eligible && opt.bgzf && (in.textMode || (facts.bam && opt.deviceGzip))) eligible = devBgzf = frame_on_all(api.set_gzip_framing, ctxs);
     if (eligible && in.textMode) devGz = enable_on_all(api.set_text_gzip, api.wait_text_gz != nullptr, ctxs);
     /* the same for BAM input (fpl_set_bam_gzip / fpl_wait_bam_gz, C-ABI version 10): the device composes the member from the
        records' names and the bases it decoded, under the same conditions with "parsed on the device" replaced by "BAM-backed
@@ -288,7 +293,10 @@ void Pipeline::enable_device_gzip() {
        decoded arrays are not even copied back (seq_out / qual_out NULL): the host formats nothing of such a batch. */
     if (eligible && facts.bam && opt.deviceGzip) devBamGz = enable_on_all(api.set_bam_gzip, api.wait_bam_gz != nullptr, ctxs);
     bamKeepArrays = !devBamGz || out.ffail; /* (--failed_out is formatted on the host: it needs the decoded bases) */
-    if ((devGz || devBamGz) && opt.verbose) cerr << "output: gzip members deflated on the device" << endl;
+    devBgzf = devBgzf && (devGz || devBamGz);
+    if ((devGz || devBamGz) && !opt.bgzf && opt.verbose) cerr << "output: gzip members deflated on the device" << endl;
+    if (opt.bgzf && opt.verbose)
+        cerr << "output: BGZF blocks" << (devBgzf ? ", deflated and framed on the device (a batch that falls back: by the host)" : ", deflated and framed by the host") << endl;
 }
 
 /* ---- stage 1: batches in input order -> devq (round-robin over the devices) */
@@ -409,6 +417,11 @@ class DeviceStage {
     void take_member(Work* w, const uint8_t* gzp, uint64_t gzn) {
         w->gz_member.assign((const char*)gzp, (size_t)gzn);
         w->dev_gz = true;
+        if (p.devBgzf) { /* (BSIZE at byte 16 of every block: the device's blocks all have the 18-byte header) */
+            uint64_t blocks = 0;
+            for (uint64_t at = 0; at + 18 <= gzn; at += 1u + gzp[at + 16] + 256u * gzp[at + 17]) blocks++;
+            p.nDevBgzf += blocks;
+        }
         p.nDevGz++;
     }
     size_t n_pending() const {

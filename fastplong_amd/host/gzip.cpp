@@ -28,6 +28,7 @@ struct Deflate {
     void* (*alloc_compressor)(int) = nullptr;
     size_t (*gzip_compress)(void*, const void*, size_t, void*, size_t) = nullptr;
     size_t (*gzip_compress_bound)(void*, size_t) = nullptr;
+    size_t (*deflate_compress)(void*, const void*, size_t, void*, size_t) = nullptr; /* (raw: bgzf_into; zlib without it) */
     void (*free_compressor)(void*) = nullptr;
     void* (*alloc_decompressor)() = nullptr;
     int (*gzip_decompress_ex)(void*, const void*, size_t, void*, size_t, size_t*, size_t*) = nullptr;
@@ -42,6 +43,7 @@ struct Deflate {
         alloc_compressor = (decltype(alloc_compressor))dlsym(lib, "libdeflate_alloc_compressor");
         gzip_compress = (decltype(gzip_compress))dlsym(lib, "libdeflate_gzip_compress");
         gzip_compress_bound = (decltype(gzip_compress_bound))dlsym(lib, "libdeflate_gzip_compress_bound");
+        deflate_compress = (decltype(deflate_compress))dlsym(lib, "libdeflate_deflate_compress");
         free_compressor = (decltype(free_compressor))dlsym(lib, "libdeflate_free_compressor");
         alloc_decompressor = (decltype(alloc_decompressor))dlsym(lib, "libdeflate_alloc_decompressor");
         gzip_decompress_ex = (decltype(gzip_decompress_ex))dlsym(lib, "libdeflate_gzip_decompress_ex");
@@ -105,6 +107,64 @@ void gzip_into(const string& in, int level, string& out) {
     const size_t n = zs.total_out;
     deflateEnd(&zs);
     out.assign(scratch.data(), n); /* (when out is the input itself: shrinks inside its own allocation) */
+}
+
+const string& bgzf_eof() {
+    static const string e("\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00\x42\x43\x02\x00\x1b\x00\x03\x00\x00\x00\x00\x00\x00\x00\x00\x00", 28);
+    return e;
+}
+void bgzf_into(const string& in, int level, string& out) {
+    constexpr size_t HEAD = 18, TAIL = 8, MAX_BLOCK = 65536, ROOM = MAX_BLOCK - HEAD - TAIL;
+    static thread_local string blocks; /* (the calling thread's, like gzip_into's scratch) */
+    blocks.clear();
+    const size_t n_pieces = (in.size() + BGZF_PIECE - 1) / BGZF_PIECE;
+    blocks.reserve(in.size() / 2 + n_pieces * (HEAD + TAIL + 5) + 64);
+    const Deflate& d = deflate_lib();
+    const bool use_lib = d.lib && d.deflate_compress;
+    static thread_local ThreadCodec tc;
+    z_stream zs;
+    memset(&zs, 0, sizeof(zs));
+    if (use_lib) {
+        if (!tc.comp || tc.level != level) {
+            if (tc.comp) d.free_compressor(tc.comp);
+            tc.comp = d.alloc_compressor(level);
+            tc.level = level;
+            if (!tc.comp) error_exit("libdeflate_alloc_compressor failed");
+        }
+    } else if (n_pieces && deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
+        error_exit("deflateInit2 failed");
+    }
+    unsigned char body[ROOM];
+    for (size_t at = 0; at < in.size(); at += BGZF_PIECE) {
+        const unsigned char* src = (const unsigned char*)in.data() + at;
+        const size_t n = min(BGZF_PIECE, in.size() - at);
+        size_t m = 0;
+        if (use_lib) {
+            m = d.deflate_compress(tc.comp, src, n, body, ROOM); /* (0: it does not fit) */
+        } else {
+            deflateReset(&zs);
+            zs.next_in = (Bytef*)src, zs.avail_in = (uInt)n;
+            zs.next_out = body, zs.avail_out = (uInt)ROOM;
+            if (deflate(&zs, Z_FINISH) == Z_STREAM_END) m = ROOM - zs.avail_out;
+        }
+        if (m == 0) { /* one final stored block: 5 + 65 280 bytes always fit */
+            body[0] = 1;
+            body[1] = (unsigned char)(n & 0xFF), body[2] = (unsigned char)(n >> 8);
+            body[3] = (unsigned char)(~n & 0xFF), body[4] = (unsigned char)((~n >> 8) & 0xFF);
+            memcpy(body + 5, src, n);
+            m = 5 + n;
+        }
+        const size_t bsize = HEAD + m + TAIL - 1;
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, (uInt)n);
+        const unsigned char head[HEAD] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (unsigned char)(bsize & 0xFF), (unsigned char)(bsize >> 8)};
+        unsigned char tail[TAIL];
+        for (int k = 0; k < 4; k++) tail[k] = (unsigned char)(crc >> (8 * k)), tail[4 + k] = (unsigned char)((uint32_t)n >> (8 * k));
+        blocks.append((const char*)head, HEAD);
+        blocks.append((const char*)body, m);
+        blocks.append((const char*)tail, TAIL);
+    }
+    if (!use_lib && n_pieces) deflateEnd(&zs);
+    out.assign(blocks);
 }
 
 int gunzip_member_into(const unsigned char* in, size_t in_len, char* out, size_t out_cap, size_t* consumed, size_t* produced) {

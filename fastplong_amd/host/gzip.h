@@ -28,6 +28,13 @@ namespace fplh {
  * the system has libdeflate.so.0), zlib otherwise. */
 void gzip_into(const std::string& in, int level, std::string& out);
 std::string gzip_member(const std::string& in, int level);
+/* The same text as BGZF blocks (the container bgzip, samtools and this project's device readers take block by block): `in` cut
+ * every BGZF_PIECE bytes (htslib's size), each piece deflated raw at `level` by the library gzip_into would use and framed with
+ * the 18-byte header (BC extra field, BSIZE), CRC-32 and ISIZE of that piece; a piece that would not fit 65 536 - 26 bytes is
+ * stored instead.  Empty input gives no bytes.  out may be the input itself.  A BGZF FILE ends with bgzf_eof(). */
+constexpr size_t BGZF_PIECE = 65280;
+void bgzf_into(const std::string& in, int level, std::string& out);
+const std::string& bgzf_eof(); /* the 28-byte empty block */
 /* bytes without std::vector's zero fill (an inflate target is overwritten anyway, and its size is a guess) */
 struct RawBuf {
     char* p = nullptr;

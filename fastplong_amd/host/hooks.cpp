@@ -211,6 +211,15 @@ uint64_t fplh_gz_members(void) { return fplh::GzMembers::delivered.exchange(0); 
 char* fplh_gunzip_to_memory(const char* path, int threads, uint64_t max_bytes, uint64_t* size_out, uint64_t* reserved) {
     return fplh::gunzip_members_to_memory(path, threads, max_bytes, size_out, reserved);
 }
+/* test hook: fplh::bgzf_into -> a malloc'ed buffer the caller frees with fplh_free (NULL and 0 for empty input) */
+int fplh_bgzf_into(const char* in, uint64_t n, int level, char** out, uint64_t* out_len) {
+    std::string s(in ? in : "", (size_t)n), o;
+    fplh::bgzf_into(s, level, o);
+    *out_len = o.size();
+    *out = o.empty() ? nullptr : (char*)malloc(o.size());
+    if (*out) memcpy(*out, o.data(), o.size());
+    return 0;
+}
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */
 void fplh_set_gzip_inflater(fplh::GzipInflateFn fn, void* user, uint64_t window_bytes) { fplh::set_gzip_inflater(fn, user, window_bytes); }

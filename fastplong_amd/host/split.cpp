@@ -13,8 +13,8 @@ using namespace std;
 
 namespace fplh {
 
-SplitOutput::SplitOutput(const string& out, int digits, int workers, bool by_lines, int number, long size, int gz_level)
-    : out_(out), digits_(digits), T_(workers), by_lines_(by_lines), number_(number), size_(size), level_(gz_level), w_(workers) {
+SplitOutput::SplitOutput(const string& out, int digits, int workers, bool by_lines, int number, long size, int gz_level, bool bgzf)
+    : out_(out), digits_(digits), T_(workers), by_lines_(by_lines), number_(number), size_(size), level_(gz_level), bgzf_(bgzf), w_(workers) {
     gz_ = out_.size() > 3 && out_.compare(out_.size() - 3, 3, ".gz") == 0;
     for (int t = 0; t < T_; t++) {
         w_[t].working = t; /* mWorkingSplit = threadId */
@@ -131,7 +131,9 @@ void SplitOutput::put(Worker& w, const char* p, size_t n) {
 void SplitOutput::flush(Worker& w) {
     if (w.pending.empty() || w.fd < 0) return;
     if (gz_) {
-        const string bytes = gzip_member(w.pending, level_);
+        string bytes;
+        if (bgzf_) bgzf_into(w.pending, level_, bytes);
+        else gzip_into(w.pending, level_, bytes);
         put(w, bytes.data(), bytes.size());
     } else {
         put(w, w.pending.data(), w.pending.size());
@@ -142,7 +144,9 @@ void SplitOutput::flush(Worker& w) {
 void SplitOutput::shut(Worker& w) {
     if (w.fd < 0) return;
     flush(w);
-    if (gz_ && !w.wrote) {
+    if (gz_ && bgzf_) { /* every BGZF file ends with the EOF block */
+        put(w, bgzf_eof().data(), bgzf_eof().size());
+    } else if (gz_ && !w.wrote) {
         const string e = gzip_member(string(), level_);
         put(w, e.data(), e.size());
     }

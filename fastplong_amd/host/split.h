@@ -34,7 +34,8 @@ namespace fplh {
  * every pack is handed to them (the S_* commands of the test harness). */
 class SplitOutput {
    public:
-    SplitOutput(const std::string& out, int digits, int workers, bool by_lines, int number, long size, int gz_level);
+    /* bgzf: .gz files are BGZF blocks (bgzf_into) ended by the EOF block instead of gzip members */
+    SplitOutput(const std::string& out, int digits, int workers, bool by_lines, int number, long size, int gz_level, bool bgzf = false);
     ~SplitOutput();
     void write(int t, const std::string& text);
     /* the same bytes as a gather list (plain files only): what is pending for worker t goes out first, then the list, by
@@ -80,6 +81,7 @@ class SplitOutput {
     long size_;
     int level_;
     bool gz_ = false;
+    bool bgzf_ = false;
     std::vector<Worker> w_;
     std::vector<std::thread> threads_;
     bool closed_ = false;

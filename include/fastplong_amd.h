@@ -437,6 +437,28 @@ int fpl_set_bam_gzip(fpl_ctx* ctx, int on);
 int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len);
 
 /*
+ * The container of a gzip batch's bytes.  FPL_ABI_VERSION stays 10: found by symbol lookup like the inflater calls below; a
+ * library without it writes members only, and its caller frames on the host.
+ *
+ *   fpl_set_gzip_framing  per context; applies to every kind that can return gzip bytes (text, BGZF text, BAM, BGZF BAM) and takes
+ *                      effect with the NEXT submission: a batch keeps the framing the context had when it was submitted, so a
+ *                      switch with batches in flight is safe.  Other values: FPL_ERR_ARG, and nothing changes.
+ *     FPL_GZIP_MEMBER  (the default) one gzip member per batch, as documented above.
+ *     FPL_GZIP_BGZF    a whole number of BGZF blocks per batch.  Block k holds exactly bytes [k * 49 152, min((k + 1) * 49 152,
+ *                      n)) of the batch's n bytes of text (49 152 = 3 * FPL_GZ_BLOCK_BYTES): an 18-byte header (1f 8b 08 04, no
+ *                      time, XFL 0, OS ff, XLEN 6, 'B' 'C' 2 0, BSIZE = the block's bytes - 1), the deflate blocks of that
+ *                      stripe -- BFINAL 0, each followed by its aligning empty stored block; dynamic blocks declare two distance
+ *                      codes of length 1, a complete set --, one final empty stored block 01 00 00 ff ff, then CRC-32 and ISIZE
+ *                      of the BLOCK's bytes.  Every block but the last has ISIZE 49 152; no block is larger than 49 152 + 5 * 53
+ *                      + 31 bytes.  Blocks of successive batches appended to a file, then the 28-byte BGZF EOF block (the
+ *                      caller's), are a BGZF file: fpl_inflate_bgzf and fpl_process_bgzf_text_async take every block of it.
+ *                      Size: never more than n + 5 * (deflate blocks) + 31 * ceil(n / 49 152) bytes.  The inflated bytes, the
+ *                      empty output (no read passed: *gz_len 0) and the lifetime are those of the member form.
+ */
+enum { FPL_GZIP_MEMBER = 0, FPL_GZIP_BGZF = 1 };
+int fpl_set_gzip_framing(fpl_ctx* ctx, int framing);
+
+/*
  * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
  * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
  * caller then inflates on the host.

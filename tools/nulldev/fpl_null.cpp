@@ -284,6 +284,11 @@ int fpl_wait_bam_gz(fpl_ctx* ctx, const uint8_t** gz, uint64_t* gz_len) {
     *gz_len = 0;
     return fpl_wait(ctx);
 }
+/* (no coder, so nothing to frame: BGZF framing is refused and a host frames its own blocks) */
+int fpl_set_gzip_framing(fpl_ctx* ctx, int framing) {
+    if (!ctx || (framing != FPL_GZIP_MEMBER && framing != FPL_GZIP_BGZF)) return FPL_ERR_ARG;
+    return framing == FPL_GZIP_BGZF ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
 /* (BGZF inflate: no device, so no inflater -- a host that finds the calls gets no handle and inflates itself) */
 fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
 int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
