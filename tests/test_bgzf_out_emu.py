@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from fastplong_amd import abi, bgzf, synth
-from tests import hostio
+from tests import gz_cases, hostio
 from tests.bgzf_out_cases import (EDGE_TOTALS, STRIPE, check_blocks, exact_text, forced_starts_text, lengths, one_long_read_text,
                                   short_reads_text)
 from tests.emu_bgzf import build as emu_inflate
@@ -109,3 +109,26 @@ def test_golden_through_the_oracle(orc, hostlib, tmp_path, case):
     res, _ = orc.process_batch(cfg, seq, qual, off)
     data, info = check(hostlib, tmp_path, text, res, case)
     assert b"".join(bgzf.inflate_block(data, o) for o in bgzf.blocks(data)[1]) == gz(os.path.join(GOLD, case, "expected.out.fq.gz"))
+
+
+@pytest.mark.parametrize("n_reads, per", [(530, 2), (1400, 3), (4300, 9)])
+def test_more_than_1024_deflate_blocks(hostlib, tmp_path, n_reads, per):
+    """k_gz_finish_bgzf gives each of its 1 024 threads a run of `per` consecutive blocks: runs that cross stripes, more than one
+    trip of the eight-loads loop, a clamped last run, threads with no run, and further trips of both finishes' prefix sums"""
+    text = gz_cases.many_blocks_text(n_reads)
+    data, info = check(hostlib, tmp_path, text, whole(lengths(text)), "%d reads" % n_reads)
+    nb = info["n_blocks"]
+    assert nb == len(gz_cases.block_starts(text)) >= 2 * n_reads
+    assert gz_cases.per_thread_runs(nb) == per and nb > 1024 * (per - 1) and nb % per != 0
+    assert len(bgzf.blocks(data)[0]) == -(-len(text) // STRIPE) >= 23  # (49 deflate blocks a stripe: runs cross stripes all along)
+
+
+def test_battery_in_name_lines(hostlib, tmp_path):
+    """the inputs that reach the coder's limits (tests/gz_cases.py) with two distance lengths in every header; check() hands the
+    blocks to the device's inflater too, whose bit-serial walk takes the 15-bit codes"""
+    text, where = gz_cases.as_fastq(gz_cases.block_battery())
+    data, info = check(hostlib, tmp_path, text, whole(lengths(text)), "battery")
+    blocks = gz_cases.bgzf_blocks(data, text)
+    assert len(blocks) == info["n_blocks"]
+    for name, m in gz_cases.check_battery(blocks, where, 2).items():
+        print(gz_cases.excess_line(name, m))

@@ -17,9 +17,11 @@ import numpy as np
 import pytest
 
 from fastplong_amd import abi, bgzf, build, synth
-from tests import bamio, hostio
+from tests import bamio, gz_cases, hostio
 from tests.bgzf_out_cases import (EDGE_TOTALS, STRIPE, check_blocks, exact_text, forced_starts_text, one_long_read_text,
                                   short_reads_text)
+from tests.emu_bgzfout import build as emu_bgzfout
+from tests.emu_gz import build as emu_gz
 from tests.gzcheck import GOLD, gz, host_format, inflate_all, load_hostlib
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +149,59 @@ def test_short_reads_merged_blocks(engine_mod, hostlib, inflater, tmp_path):
 def test_one_read_over_nine_stripes(engine_mod, hostlib, inflater, tmp_path):
     data, want = text_case(engine_mod, hostlib, inflater, tmp_path, one_long_read_text(), PLAIN, "one long read", C=200_000)
     assert len(bgzf.blocks(data)[0]) == 9
+
+
+def test_battery_in_name_lines(engine_mod, hostlib, inflater, tmp_path):
+    """the inputs that reach the coder's limits (tests/gz_cases.py) through k_gz_block_bgzf and k_gz_block: every deflate block
+    meets gz_cases.check_block, the device's inflater takes the BGZF blocks back (15-bit codes go down its bit-serial walk), and
+    both outputs are, byte for byte, the emulator's for the same text and records"""
+    text, where = gz_cases.as_fastq(gz_cases.block_battery())
+    res, data, _ = run_text(engine_mod, text, PLAIN, True)
+    res_m, member, _ = run_text(engine_mod, text, PLAIN, False)
+    want = host_format(hostlib, tmp_path, text, res)
+    assert want == text and res.tobytes() == res_m.tobytes()
+    check_device_blocks(inflater, data, member, want, "battery")
+    blocks = gz_cases.bgzf_blocks(data, want)
+    for name, m in gz_cases.check_battery(blocks, where, 2).items():
+        print(gz_cases.excess_line(name, m))
+    gz_cases.check_battery(gz_cases.member_blocks(member, want), where, 1)
+    emu, _ = emu_bgzfout.emit(text, res, True)
+    emu_blocks = gz_cases.bgzf_blocks(emu, want)
+    assert [b["raw"] == e["raw"] for b, e in zip(blocks, emu_blocks)] == [True] * len(emu_blocks), [b["start"] for b in blocks]
+    assert data == emu
+    assert member == emu_gz.emit(text, res)[0]
+
+
+def test_tail_lengths(engine_mod, hostlib, inflater, tmp_path):
+    """a last deflate block of every length at the edges of a thread's stretch and of the 16-byte loads and stores, in a BGZF
+    block of its own (the text is one stripe and the tail)"""
+    eng = new_engine(engine_mod, PLAIN, True)
+    for r in gz_cases.TAIL_LENGTHS:
+        text = gz_cases.tail_text(r)
+        eng.submit_text(pinned(eng, text), gzip=True)
+        info, res, lines, data = eng.wait_text()
+        assert info["status"] == abi.FPL_TEXT_OK and (res["code"][:, 0] == abi.FPL_PASS_FILTER).all() and (res["n_frag"] == 1).all()
+        frames = check_blocks(data, text, piece=STRIPE)
+        assert len(frames) == 2
+        blocks = gz_cases.bgzf_blocks(data, text)
+        assert len(blocks) == 4 and blocks[-1]["n"] == r
+        for b in blocks:
+            gz_cases.check_block(b, 2)
+        desc, _ = bgzf.blocks(data)
+        out, status = inflater.inflate(np.frombuffer(data, np.uint8), desc)
+        assert (status == 0).all() and out.tobytes() == text, r
+    eng.close()
+
+
+@pytest.mark.parametrize("n_reads, per", [(530, 2), (4300, 9)])
+def test_more_than_1024_deflate_blocks(engine_mod, hostlib, inflater, tmp_path, n_reads, per):
+    """k_gz_finish_bgzf's threads take runs of `per` consecutive deflate blocks that cross stripes, and both finishes' prefix sums
+    go round more than once (tests/test_bgzf_out_emu.py has the list of what only runs then)"""
+    text = gz_cases.many_blocks_text(n_reads)
+    nb = deflate_blocks(text)
+    assert gz_cases.per_thread_runs(nb) == per and nb > 1024 * (per - 1) and nb % per != 0
+    data, want = text_case(engine_mod, hostlib, inflater, tmp_path, text, PLAIN, "%d reads" % n_reads)
+    assert want == text and len(bgzf.blocks(data)[0]) == -(-len(text) // STRIPE) >= 23
 
 
 def ont_text():

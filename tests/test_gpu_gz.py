@@ -11,11 +11,13 @@ import numpy as np
 import pytest
 
 from fastplong_amd import abi, build, synth
-from tests import hostio
+from tests import gz_cases, hostio
+from tests.emu_gz import build as emu_gz
 from tests.gzcheck import GOLD, gz, host_format, inflate_all, load_hostlib
 
 pytestmark = pytest.mark.gpu
 
+PLAIN = dict(adapter_enabled=0, qual_filter=0, length_filter=0)  # the output is the input
 C3 = dict(cut_front=1, cut_tail=1, cut_front_window=5, cut_tail_window=5, polyx=1, complexity_filter=1)
 
 
@@ -120,6 +122,50 @@ def test_batches_in_flight_switch_per_batch_and_empty_output(engine_mod, hostlib
     info, res, lines, member = eng.wait_text()
     assert info["status"] == abi.FPL_TEXT_OK and info["n_reads"] == 300 and member == b"" and eng.gzip_batches() == 0
     eng.close()
+
+
+def _plain_members(engine_mod, texts, C=20480):
+    """the members of `texts`, one submission each on ONE engine that changes nothing -> [(records, member)]"""
+    eng = engine_mod.Engine(abi.FplOptions.default(**PLAIN), "", "", device=0, max_cycles=C)
+    out = []
+    for text in texts:
+        eng.submit_text(_pinned(eng, text), gzip=True)
+        info, res, lines, member = eng.wait_text()
+        assert info["status"] == abi.FPL_TEXT_OK
+        out.append((res, member))
+    assert eng.gzip_batches() == len(texts)
+    eng.close()
+    return out
+
+
+def test_battery_in_name_lines(engine_mod, hostlib, tmp_path):
+    """the inputs that reach the coder's limits (tests/gz_cases.py: 15-bit and 7-bit limits, the stored form, two- and three-symbol
+    blocks, 250+ symbols, bytes from 0x80 up) through k_gz_block: every block meets gz_cases.check_block, and the member is, byte for
+    byte, the emulator's -- the coder is deterministic, and a difference says which block the device got wrong"""
+    text, where = gz_cases.as_fastq(gz_cases.block_battery())
+    (res, member), = _plain_members(engine_mod, [text])
+    want = host_format(hostlib, tmp_path, text, res)
+    assert want == text and inflate_all(member, len(want)) == want
+    blocks = gz_cases.member_blocks(member, want)
+    for name, m in gz_cases.check_battery(blocks, where, 1).items():
+        print(gz_cases.excess_line(name, m))
+    emu, _ = emu_gz.emit(text, res)
+    emu_blocks = gz_cases.member_blocks(emu, want)
+    assert [b["raw"] == e["raw"] for b, e in zip(blocks, emu_blocks)] == [True] * len(emu_blocks), [b["start"] for b in blocks]
+    assert member == emu
+
+
+def test_tail_lengths(engine_mod, hostlib, tmp_path):
+    """a last block of every length at the edges of a thread's stretch of 64 symbols and of the 16-byte loads and stores"""
+    texts = [gz_cases.tail_text(r) for r in gz_cases.TAIL_LENGTHS]
+    for r, text, (res, member) in zip(gz_cases.TAIL_LENGTHS, texts, _plain_members(engine_mod, texts)):
+        assert len(res) == text.count(b"\n") // 4 and (res["code"][:, 0] == abi.FPL_PASS_FILTER).all() and (res["n_frag"] == 1).all()
+        assert inflate_all(member, len(text)) == text, r
+        blocks = gz_cases.member_blocks(member, text)
+        assert len(blocks) == 4 and blocks[-1]["n"] == r
+        for b in blocks:
+            gz_cases.check_block(b, 1)
+        assert member == emu_gz.emit(text, res)[0], r
 
 
 GOLDEN_TEXT = ["c1_qualfilter", "c3_full", "c5_fasta"]  # (--break / --mask output keeps the host's deflate: never a text batch)

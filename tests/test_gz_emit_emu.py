@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from fastplong_amd import abi, build, synth
-from tests import hostio
+from tests import gz_cases, hostio
+from tests.bgzf_out_cases import exact_text, lengths
 from tests.emu_gz import build as emu_gz
 from tests.gzcheck import GOLD, GOLDEN_OPTS, fasta_list, gz, host_format, inflate_all, load_hostlib, parse_fastq
 
@@ -194,9 +195,16 @@ def test_fibonacci_name_needs_the_length_limit(hostlib, tmp_path):
     reads = [(b"@" + name.tobytes(), b"ACGT" * 50, b"+", b"I" * 200)]
     data, info, want = check(hostlib, tmp_path, fastq(reads), whole([200]))
     assert len(data) < len(want) // 2  # (coded, not stored)
-    # and every count in ONE block, in order: depth 15 is reached with 16 384 bytes
-    g, d = emu_gz.deflate(np.sort(name)[::-1][:emu_gz.block_bytes()].tobytes())
-    assert inflate_all(g, d["total"]) == np.sort(name)[::-1][:emu_gz.block_bytes()].tobytes()
+    # ... but cut into blocks of 16 384 bytes no block's tree is deeper than 15: every block costs exactly the optimum
+    ms = [gz_cases.check_block(b, 1) for b in gz_cases.member_blocks(data, want)]
+    assert all(not m["stored"] and m["depth"] <= 15 and m["cost"] == m["optimum"] for m in ms)
+    # the limit is reached by Lucas counts in ONE block: the unlimited tree is 18 deep, the longest code has 15 bits
+    blk = gz_cases.block_battery()["lucas_sorted"]
+    g, d = emu_gz.deflate(blk)
+    assert inflate_all(g, d["total"]) == blk
+    m = gz_cases.check_block(gz_cases.member_blocks(g, blk, [0])[0], 1)
+    gz_cases.check_case("lucas_sorted", m, alone=True)
+    assert m["depth"] == 18 and m["longest"] == 15 and m["optimum"] == 39566
 
 
 def test_random_name_is_stored(hostlib, tmp_path):
@@ -223,3 +231,61 @@ def test_crc_stage_at_stretch_boundaries():
     text = (b"@q\nACGTTGCA\n+\nIIIIHHHH\n") * 3000
     g, d = emu_gz.deflate(text)
     assert d["crc"] == zlib.crc32(text) and inflate_all(g, len(text)) == text
+
+
+def test_the_reference_itself():
+    """tests/gz_cases.py against itself and against zlib: the length-limited optimum is the Huffman cost when the limit does not
+    bind, never falls when the limit shrinks, and the header parser reads what zlib writes"""
+    rng = np.random.default_rng(13)
+    for k in range(40):
+        f = (rng.geometric(rng.uniform(0.002, 0.5), int(rng.integers(1, 258))) - 1) * (rng.random() < 0.8 or 1)
+        depth, cost = gz_cases.huffman_depth(f), gz_cases.huffman_cost(f)
+        assert gz_cases.package_merge(f, max(depth, 1)) == cost == gz_cases.package_merge(f, 32)
+        if depth > 9:
+            assert gz_cases.package_merge(f, depth - 1) > cost
+            assert gz_cases.package_merge(f, 9) >= gz_cases.package_merge(f, 10) >= cost
+    assert gz_cases.package_merge([1, 1, 2, 3, 5, 8, 13], 3) == 2 * 13 + 3 * 20  # (7 leaves in 3 bits: one code of 2 bits, the commonest symbol's)
+    assert gz_cases.huffman_depth([1, 1] + gz_cases.lucas_counts()[1:]) == 18
+    text = exact_text(9000)
+    c = zlib.compressobj(9, zlib.DEFLATED, -15, 9, zlib.Z_HUFFMAN_ONLY)
+    raw = c.compress(text) + c.flush()
+    h = gz_cases.parse_dynamic_header(raw)
+    freqs = np.bincount(np.frombuffer(text, np.uint8), minlength=257)
+    freqs[256] = 1
+    lens = np.array(h["lit"] + [0] * (257 - len(h["lit"])))[:257]
+    assert h["final"] == 1 and ((lens > 0) == (freqs > 0)).all() and gz_cases.kraft(lens, 15) == 1 << 15
+    assert int((freqs * lens).sum()) == gz_cases.huffman_cost(freqs) == gz_cases.package_merge(freqs, 15)
+    assert h["end"] + int((freqs * lens).sum()) <= 8 * len(raw) < h["end"] + int((freqs * lens).sum()) + 8
+
+
+@pytest.mark.parametrize("name", gz_cases.BATTERY_NAMES)
+def test_battery_block_alone(name):
+    """every input that reaches a limit of the coder (tests/gz_cases.py), as a deflate block of its own"""
+    blk = gz_cases.block_battery()[name]
+    g, d = emu_gz.deflate(blk)
+    assert inflate_all(g, len(blk)) == blk and d["crc"] == zlib.crc32(blk) and d["n_blocks"] == 1
+    m = gz_cases.check_block(gz_cases.member_blocks(g, blk, [0])[0], 1)
+    print(gz_cases.excess_line(name, m))
+    gz_cases.check_case(name, m, alone=True)
+
+
+def test_battery_in_name_lines(hostlib, tmp_path):
+    """the battery through the layout, the compose and the block kernels: FASTQ with every block in a name line"""
+    text, where = gz_cases.as_fastq(gz_cases.block_battery())
+    data, info, want = check(hostlib, tmp_path, text, whole(lengths(text)))
+    assert want == text
+    blocks = gz_cases.member_blocks(data, want)
+    assert len(blocks) == info["n_blocks"]
+    for name, m in gz_cases.check_battery(blocks, where, 1).items():
+        print(gz_cases.excess_line(name, m))
+
+
+def test_tail_lengths(hostlib, tmp_path):
+    """the last block's length at the edges of a thread's stretch of 64 symbols and of the 16-byte loads and stores"""
+    for r in gz_cases.TAIL_LENGTHS:
+        text = gz_cases.tail_text(r)
+        data, info, want = check(hostlib, tmp_path, text, whole(lengths(text)))
+        blocks = gz_cases.member_blocks(data, want)
+        assert want == text and len(blocks) == info["n_blocks"] == 4 and blocks[-1]["n"] == r
+        for b in blocks:
+            gz_cases.check_block(b, 1)
