@@ -28,6 +28,8 @@ FPL_ERR_STATE = -6
 
 FPL_GZIP_MEMBER = 0  # fpl_set_gzip_framing
 FPL_GZIP_BGZF = 1
+FPL_GZIP_FASTQ = 0  # fpl_set_gzip_records
+FPL_GZIP_BAM = 1
 
 FPL_TEXT_OK = 0
 FPL_TEXT_IRREGULAR = 1

@@ -12,6 +12,25 @@ from . import abi
 EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
+# the fixed header of every BAM file this project writes (README "BAM output"): magic, l_text, the text, n_ref = 0
+BAM_HEADER_TEXT = b"@HD\tVN:1.6\tSO:unknown\n@PG\tID:fastplong_amd\tPN:fastplong_amd\n"
+
+
+def eof():
+    """the 28-byte block that ends a BGZF file"""
+    return EOF
+
+
+def bam_header():
+    """the BGZF block that opens a BAM file of Engine.set_gzip_records(True) batches: header + the batches' bytes + eof().
+    The 72 bytes are stored, not deflated: every inflater takes that, the device's strict one included."""
+    raw = b"BAM\1" + struct.pack("<i", len(BAM_HEADER_TEXT)) + BAM_HEADER_TEXT + struct.pack("<i", 0)
+    c = zlib.compressobj(0, zlib.DEFLATED, -15)
+    body = c.compress(raw) + c.flush()
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", 18 + len(body) + 8 - 1) + body +
+            struct.pack("<II", zlib.crc32(raw) & 0xFFFFFFFF, len(raw)))
+
+
 class BgzfError(ValueError):
     pass
 

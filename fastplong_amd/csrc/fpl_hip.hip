@@ -26,6 +26,7 @@
 #include "buf.h"
 #include "text_parse.h"
 #include "gz_emit.h"
+#include "bam_emit.h"
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
 #include "bam_walk.h"

@@ -37,6 +37,9 @@
  *   k_gz_frame        a thread per stripe: header with BSIZE, final empty block, CRC-32 and ISIZE of the stripe
  *   k_gz_compact      unchanged
  * Worst case: gz_len <= total + GZ_SLACK * n_blocks + GZ_BGZF_EXTRA * ceil(total / GZ_STRIPE) (beside GZ_STRIPE below).
+ *
+ * The layout body is also templated on the FORM of the composed bytes (GzFastqForm here); csrc/bam_emit.h has the form of unaligned
+ * BAM records (fpl_set_gzip_records), a compose kernel of its own, and runs the BGZF block kernels on what it composes.
  */
 #ifndef FPL_GZ_EMIT_H
 #define FPL_GZ_EMIT_H
@@ -211,6 +214,12 @@ __device__ __forceinline__ void gz_frag_len(const GzRec& g, const fpl_read_resul
     a = (u64)g.name_len + gz_prefix_len(r.kind[f], g.name_len) + 1 + (u64)r.frag_len[f] + 1;
     b = (u64)g.strand_len + 1 + (u64)r.frag_len[f] + 1;
 }
+/* the form of the composed bytes: what a fragment writes in front of its second forced cut (a) and behind it (b).  FASTQ text here;
+   csrc/bam_emit.h has the BAM records' form.  prep: once per record, before the lengths are asked for. */
+struct GzFastqForm {
+    static __device__ __forceinline__ void prep(GzRec&) {}
+    static __device__ __forceinline__ void frag_len(const GzRec& g, const fpl_read_result& r, int f, u64& a, u64& b) { gz_frag_len(g, r, f, a, b); }
+};
 /* the block starts inside [s, e): s itself when forced or on a multiple of GZ_B, and every multiple of GZ_B behind it */
 template <class F>
 __device__ __forceinline__ void gz_cuts(u64 s, u64 e, bool force, F&& emit) {
@@ -218,13 +227,13 @@ __device__ __forceinline__ void gz_cuts(u64 s, u64 e, bool force, F&& emit) {
     if (force || s % GZ_B == 0) emit(s);
     for (u64 m = (s / GZ_B + 1) * GZ_B; m < e; m += GZ_B) emit(m);
 }
-template <class F>
+template <class Form = GzFastqForm, class F>
 __device__ __forceinline__ void gz_read_cuts(const GzRec& g, const fpl_read_result& r, u64 o, F&& emit) {
     if (r.dropped) return;
     for (int f = 0; f < r.n_frag && f < 2; f++) {
         if (r.code[f] != FPL_PASS_FILTER) continue;
         u64 a, b;
-        gz_frag_len(g, r, f, a, b);
+        Form::frag_len(g, r, f, a, b);
         if ((u64)r.frag_len[f] + 1 >= GZ_L) {
             gz_cuts(o, o + a, true, emit);
             gz_cuts(o + a, o + a + b, true, emit);
@@ -247,7 +256,7 @@ __device__ __forceinline__ u64 gz_scan_incl_u64(u64 v) {
 
 /* one block.  rec_off[r] = where record r's output starts (n_rec + 1 entries), blk_start[b] = where deflate block b starts
    (n_blocks + 1 entries, the last one the total) */
-template <class Src>
+template <class Form = GzFastqForm, class Src>
 __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off,
                                                u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
     __shared__ u64 wsum[16];
@@ -261,12 +270,13 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
         u64 len = 0;
         if (i < n_rec) {
             g = src.rec(i);
+            Form::prep(g);
             r = res[i];
             if (!r.dropped)
                 for (int f = 0; f < r.n_frag && f < 2; f++)
                     if (r.code[f] == FPL_PASS_FILTER) {
                         u64 a, b;
-                        gz_frag_len(g, r, f, a, b);
+                        Form::frag_len(g, r, f, a, b);
                         len += a + b;
                     }
         }
@@ -280,7 +290,7 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
         if (threadIdx.x == 1023) carry_len = o + len;
         /* the blocks that start inside this record */
         u64 cnt = 0;
-        if (i < n_rec) gz_read_cuts(g, r, o, [&](u64) { cnt++; });
+        if (i < n_rec) gz_read_cuts<Form>(g, r, o, [&](u64) { cnt++; });
         incl = gz_scan_incl_u64(cnt);
         if (lane_id() == 63) wsum[wave_in_block()] = incl;
         __syncthreads();
@@ -288,7 +298,7 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
         for (int k = 0; k < wave_in_block(); k++) k0 += wsum[k];
         if (i < n_rec) {
             u64 k = k0;
-            gz_read_cuts(g, r, o, [&](u64 p) {
+            gz_read_cuts<Form>(g, r, o, [&](u64 p) {
                 if (k < blk_cap) blk_start[k] = p;
                 k++;
             });

@@ -126,6 +126,7 @@ struct fpl_ctx {
             PinBuf<u8> h_out;
             Event ev;
             bool bgzf = false; /* the context's framing when the batch was submitted (fpl_set_gzip_framing) */
+            bool records = false; /* ... and its form: BAM records in place of FASTQ text (fpl_set_gzip_records; BGZF always) */
         } gzip;
         /* a BAM batch: the inflated record bytes, where every record starts, and where the decoded bases go on the host (NULL: a
            gzip batch that leaves them on the device) */
@@ -168,6 +169,7 @@ struct fpl_ctx {
     bool text_gzip = false;    /* fpl_set_text_gzip */
     bool bam_gzip = false;     /* fpl_set_bam_gzip */
     bool gzip_bgzf = false;    /* fpl_set_gzip_framing: what the next gzip batch's slot records */
+    bool gzip_records = false; /* fpl_set_gzip_records: the same */
     /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the
        device (csrc/bam_walk.h, csrc/text_walk.h) */
     DevBuf<BamWalkState> d_bamw_state;

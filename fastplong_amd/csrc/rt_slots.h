@@ -40,7 +40,8 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
         FPL_HIP(g.d_hdr.alloc(1));
         FPL_HIP(g.h_hdr.alloc(1));
     }
-    const uint64_t blk_want = (bam ? gz_bam_blocks_bound(sl.bam.bases, n) : gz_blocks_bound(sl.text.bytes, n)) + 1;
+    const uint64_t blk_want = (g.records ? (bam ? bamout_bam_blocks_bound(sl.bam.bases, n) : bamout_blocks_bound(sl.text.bytes, n))
+                                         : (bam ? gz_bam_blocks_bound(sl.bam.bases, n) : gz_blocks_bound(sl.text.bytes, n))) + 1;
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
     FPL_HIP(g.d_rec_off.grow((size_t)n + 1, 4096 / sizeof(u64)));
     if (!g.d_blk_start.holds(blk_want)) {
@@ -50,11 +51,11 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
     const u32 blk_cap = (u32)g.d_blk_start.cap;
     hipStream_t st = ctx->stream;
     if (bam)
-        hipLaunchKernelGGL(k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+        hipLaunchKernelGGL(g.records ? k_bamout_layout_bam : k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
                            (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, g.d_rec_off.ptr, g.d_blk_start.ptr, blk_cap - 1, g.d_hdr.ptr);
     else
-        hipLaunchKernelGGL(k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
+        hipLaunchKernelGGL(g.records ? k_bamout_layout : k_gz_layout, dim3(1), dim3(1024), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
                            (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, g.d_rec_off.ptr, g.d_blk_start.ptr,
                            blk_cap - 1, g.d_hdr.ptr);
     FPL_HIP(hipGetLastError());
@@ -78,12 +79,13 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(g.d_tmp.grow(out_want + 16, 4096));
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
+    /* (g.records: the bytes are BAM records, csrc/bam_emit.h; the block kernels below do not care) */
     if (bam_records(sl.kind))
-        hipLaunchKernelGGL(k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+        hipLaunchKernelGGL(g.records ? k_bamout_compose_bam : k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
     else
-        hipLaunchKernelGGL(k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
+        hipLaunchKernelGGL(g.records ? k_bamout_compose : k_gz_compose, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
                            (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr,
                            g.d_comp.ptr, (u64)h.total);
     const u32 grid = std::max<u32>(1u, std::min<u32>(h.n_blocks, 8u * ctx->n_cu));
@@ -179,7 +181,8 @@ static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = kind;
     sl.gz = gz;
-    sl.gzip.bgzf = ctx->gzip_bgzf; /* (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
+    sl.gzip.records = ctx->gzip_records;
+    sl.gzip.bgzf = ctx->gzip_bgzf || sl.gzip.records; /* BAM records are BGZF whatever the framing says (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
     sl.n_reads = 0;
     sl.user_results = nullptr;
     sl.rc = FPL_OK;

@@ -118,6 +118,12 @@ int fpl_set_gzip_framing(fpl_ctx* ctx, int framing) {
     return FPL_OK;
 }
 
+int fpl_set_gzip_records(fpl_ctx* ctx, int records) {
+    if (!ctx || (records != FPL_GZIP_FASTQ && records != FPL_GZIP_BAM)) return FPL_ERR_ARG;
+    ctx->gzip_records = records == FPL_GZIP_BAM; /* (read by slot_begin, like the framing) */
+    return FPL_OK;
+}
+
 static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
                      const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;

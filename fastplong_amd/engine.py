@@ -25,7 +25,7 @@ EXPORTS = [
     "fpl_count_end_kmers", "fpl_pick_adapter", "fpl_rccl_library", "fpl_comm_init", "fpl_get_batch_forms", "fpl_assume_inputs_ready",
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
-    "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing",
+    "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing", "fpl_set_gzip_records",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
@@ -158,6 +158,9 @@ def load_library(path=None):
     if hasattr(L, "fpl_set_gzip_framing"):  # (found by name: without it Engine.set_gzip_framing raises)
         L.fpl_set_gzip_framing.restype = C.c_int
         L.fpl_set_gzip_framing.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "fpl_set_gzip_records"):  # (found by name: without it Engine.set_gzip_records raises)
+        L.fpl_set_gzip_records.restype = C.c_int
+        L.fpl_set_gzip_records.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
         L.fpl_inflater_create.restype = C.c_void_p
         L.fpl_inflater_create.argtypes = [C.c_int32]
@@ -724,6 +727,13 @@ class Engine:
         if not hasattr(self.L, "fpl_set_gzip_framing"):
             raise FplError("the loaded libfastplong_amd.so has no fpl_set_gzip_framing")
         self._check(self.L.fpl_set_gzip_framing(self.h, abi.FPL_GZIP_BGZF if bgzf else abi.FPL_GZIP_MEMBER), "fpl_set_gzip_framing")
+
+    def set_gzip_records(self, bam):
+        """fpl_set_gzip_records: the gzip batches submitted from now on are unaligned BAM records in BGZF blocks (True; a file is
+        fastplong_amd.bgzf.bam_header() + the batches' bytes + bgzf.eof()) or FASTQ text (False, the default)"""
+        if not hasattr(self.L, "fpl_set_gzip_records"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_gzip_records")
+        self._check(self.L.fpl_set_gzip_records(self.h, abi.FPL_GZIP_BAM if bam else abi.FPL_GZIP_FASTQ), "fpl_set_gzip_records")
 
     def gzip_batches(self):
         """batches whose gzip member was made on the device (fpl_get_gzip_batches)"""

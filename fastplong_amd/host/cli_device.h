@@ -36,6 +36,8 @@ struct DeviceApi {
     WaitBamGzFn wait_bam_gz = nullptr;
     /* --bgzf: the device frames its gzip batches as BGZF blocks (found by name; without it the host frames everything) */
     SetGzipFn set_gzip_framing = nullptr;
+    /* --out *.bam: the device's gzip batches are BAM records in BGZF blocks (found by name; without it the host converts and frames) */
+    SetGzipFn set_gzip_records = nullptr;
 };
 
 static DeviceApi load_device_api() {
@@ -51,11 +53,14 @@ static DeviceApi load_device_api() {
     a.set_bam_gzip = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_gzip");
     a.wait_bam_gz = (DeviceApi::WaitBamGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_bam_gz");
     a.set_gzip_framing = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_framing");
+    a.set_gzip_records = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_records");
     return a;
 }
 
-/* BGZF framing on every context or on none */
+/* BGZF framing (set_gzip_framing) or BAM records (set_gzip_records: FPL_GZIP_BAM is 1 like FPL_GZIP_BGZF) on every context or
+   on none */
 static bool frame_on_all(DeviceApi::SetGzipFn set, const vector<fpl_ctx*>& ctxs) {
+    static_assert((int)FPL_GZIP_BAM == (int)FPL_GZIP_BGZF && (int)FPL_GZIP_FASTQ == (int)FPL_GZIP_MEMBER, "one helper for both calls");
     bool on = set != nullptr;
     for (size_t d = 0; on && d < ctxs.size(); d++)
         if (set(ctxs[d], FPL_GZIP_BGZF) != FPL_OK) on = false;

@@ -32,7 +32,8 @@ static void print_pipeline_summary(const Pipeline& p) {
     }
     if (p.devBamGz || (in.textMode && p.devGz))
         cerr << "device gzip: " << p.nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
-    if (p.opt.bgzf) cerr << "BGZF blocks framed on the device: " << p.nDevBgzf.load() << " (every other block by the host)" << endl;
+    if (p.out.fout && p.out.fout.bam) cerr << "BAM records: BGZF blocks framed on the device: " << p.nDevBgzf.load() << " (every other block by the host)" << endl;
+    else if (p.opt.bgzf) cerr << "BGZF blocks framed on the device: " << p.nDevBgzf.load() << " (every other block by the host)" << endl;
     if (in.textMode)
         cerr << "device parse: " << p.nTextBatches.load() << " chunks parsed on the device, " << p.nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;

@@ -210,7 +210,7 @@ static InputPlan plan_input(const Options& opt, const InputFacts& in, const Devi
              << (p.chunkBytes >> 20) << " MB of text each); lower --chunk_mb for smaller batches" << endl;
     /* Work objects bound what is in flight: one per parser, FPL_MAX_IN_FLIGHT per device in the copy / kernel stage,
        one per device being formatted, two waiting for the writer */
-    const bool gzOut = !opt.splitEnabled && (ends_with_gz(opt.out) || ends_with_gz(opt.failedOut)); /* (then up to four batches are formatted at a time) */
+    const bool gzOut = !opt.splitEnabled && (ends_with_gz(opt.out) || ends_with_gz(opt.failedOut) || ends_with_bam(opt.out) || ends_with_bam(opt.failedOut)); /* (then up to four batches are formatted at a time) */
     /* (+ FPLH_EXTRA_WORK, default 6: with exactly as many as the stages can hold, a parser waits for a Work object while the writer
        or a formatter still holds one, and the device thread finds its queue empty -- the link then idles between two uploads) */
     const int extraWork = getenv("FPLH_EXTRA_WORK") ? atoi(getenv("FPLH_EXTRA_WORK")) : 6;

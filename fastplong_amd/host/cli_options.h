@@ -52,6 +52,7 @@ static void error_exit(const string& msg) { /* src/util.h:270-273 */
 static double now_s() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static bool ends_with_gz(const string& p) { return p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0; }
+static bool ends_with_bam(const string& p) { return p.size() > 4 && p.compare(p.size() - 4, 4, ".bam") == 0; } /* unaligned BAM output */
 
 struct Flag {
     const char* name;
@@ -326,8 +327,10 @@ static Options parse_options(int argc, char** argv) {
     p.gzStream = cmd.exist("gz_stream"), p.deviceParse = cmd.exist("device_parse"), p.hostParse = cmd.exist("host_parse");
     p.hostGzip = cmd.exist("host_gzip"), p.deviceGzip = cmd.exist("device_gzip"), p.deviceInflate = cmd.exist("device_inflate");
     p.bgzf = cmd.exist("bgzf");
-    if (p.bgzf && !((ends_with_gz(p.out) && !p.toStdout) || (!p.splitEnabled && ends_with_gz(p.failedOut))))
+    const bool bamOut = (ends_with_bam(p.out) && !p.toStdout) || (!p.splitEnabled && ends_with_bam(p.failedOut)); /* (BGZF by itself: --bgzf changes nothing for it) */
+    if (p.bgzf && !bamOut && !((ends_with_gz(p.out) && !p.toStdout) || (!p.splitEnabled && ends_with_gz(p.failedOut))))
         error_exit("--bgzf needs an output whose name ends in .gz (--out, --failed_out or the --split files)");
+    if (p.splitEnabled && ends_with_bam(p.out)) error_exit("--split / --split_by_lines do not write BAM files (--out " + p.out + ")");
 
     stringstream ss; /* src/main.cpp:252-256 */
     for (int i = 0; i < argc; i++) ss << argv[i] << " ";

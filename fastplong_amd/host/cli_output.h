@@ -5,17 +5,21 @@
 #ifndef FPLH_CLI_OUTPUT_H
 #define FPLH_CLI_OUTPUT_H
 
+#include "bam_out.h"
 #include "cli_options.h"
 #include "gzip.h"
 #include "pool.h"
 #include "split.h"
 
 /* Outputs are plain files; a name ending in .gz gets gzip members (-z level), one per formatted slice,
-   deflated on the formatter threads and concatenated by the writer: any gzip reader takes that as one stream */
+   deflated on the formatter threads and concatenated by the writer: any gzip reader takes that as one stream.
+   A name ending in .bam gets unaligned BAM (README "BAM output"): the header's BGZF block, every slice's text turned into
+   records (bam_out.h) and framed as BGZF blocks, the EOF block */
 struct OutFile {
     FILE* f = nullptr;
     bool gz = false;
     bool bgzf = false; /* --bgzf: the .gz is BGZF blocks, ended by the EOF block */
+    bool bam = false;  /* *.bam: BAM records in BGZF blocks (gz and bgzf are set too), the header in front */
     bool wrote = false;
     /* FPLH_PARALLEL_WRITE (measurement hook): the pieces of a batch written side by side at their offsets (pwrite from
        the worker pool; nothing goes through the FILE's buffer then).  Measured on the GPU box into tmpfs: no gain -- one
@@ -29,13 +33,23 @@ struct OutFile {
     static OutFile open(const string& path, bool bgzf = false) {
         OutFile o;
         if (path.empty()) return o;
-        o.gz = ends_with_gz(path);
-        o.bgzf = o.gz && bgzf;
+        o.bam = ends_with_bam(path);
+        o.gz = o.bam || ends_with_gz(path);
+        o.bgzf = o.bam || (o.gz && bgzf);
         o.f = fopen(path.c_str(), "wb");
         if (!o.f) error_exit("Failed to write: " + path);
         struct stat st;
         o.positional = getenv("FPLH_PARALLEL_WRITE") && fstat(fileno(o.f), &st) == 0 && S_ISREG(st.st_mode);
         return o;
+    }
+    /* *.bam: the header's block, before the first piece (a file no read reaches is this block and the EOF block) */
+    void write_bam_header(int gzLevel) {
+        if (!f || !bam) return;
+        string h;
+        fplh::bgzf_into(fplh::bam_header_bytes(), gzLevel, h);
+        if (positional ? pwrite(fileno(f), h.data(), h.size(), 0) != (ssize_t)h.size() : fwrite(h.data(), 1, h.size(), f) != h.size())
+            error_exit("write failed");
+        pos = h.size();
     }
     void write_pieces(const vector<string>& pieces) {
         if (positional) { /* input order by construction: the offsets are the running sum of the pieces' sizes */
@@ -96,11 +110,17 @@ struct Outputs {
     bool gatherOut = false;             /* --out is written as gather lists over the batches' own arrays (build_gather) */
 
     bool any_gz() const { return (fout && fout.gz) || (ffail && ffail.gz); }
-    void gzip_pieces(vector<string>& pieces) const { /* in parallel; pieces stay below 4 GiB (one slice of a batch) */
+    /* the pieces as `file` takes them (in parallel; pieces stay below 4 GiB: one slice of a batch) */
+    void gzip_pieces(vector<string>& pieces, const OutFile& file) const {
         const int level = gzLevel;
-        const bool blocks = bgzf;
+        const bool blocks = file.bgzf, records = file.bam;
         fplh::parallel_run((int)pieces.size(), [&](int i) {
             if (pieces[i].empty()) return;
+            if (records) {
+                string rec;
+                fplh::fastq_to_bam_records(pieces[i], rec);
+                pieces[i].swap(rec);
+            }
             if (blocks) fplh::bgzf_into(pieces[i], level, pieces[i]);
             else fplh::gzip_into(pieces[i], level, pieces[i]);
         });
@@ -118,8 +138,10 @@ static Outputs open_outputs(const Options& opt) {
     o.bgzf = opt.bgzf;
     o.fout = OutFile::open(opt.splitEnabled ? string() : opt.out, opt.bgzf);
     o.ffail = OutFile::open(opt.splitEnabled ? string() : opt.failedOut, opt.bgzf);
-    if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.bgzf = false, o.fout.positional = false;
+    if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.bgzf = false, o.fout.bam = false, o.fout.positional = false;
     o.gzLevel = min(9, max(1, opt.compression));
+    o.fout.write_bam_header(o.gzLevel);
+    o.ffail.write_bam_header(o.gzLevel);
     if (opt.splitEnabled)
         o.split = new fplh::SplitOutput(opt.out, opt.splitDigits, opt.workers, opt.splitByLines, opt.splitNumber, opt.splitSize, o.gzLevel, opt.bgzf);
     /* Plain --out alone that is NOT a regular file -- a pipe into an aligner or a compressor (--stdout, /dev/stdout), /dev/null --

@@ -199,6 +199,7 @@ struct Pipeline {
     bool devGz = false;         /* --out *.gz: text batches come back with their gzip member (fpl_wait_text_gz) */
     bool devBamGz = false;      /* ... BAM-backed batches do (fpl_wait_bam_gz) */
     bool devBgzf = false;       /* --bgzf: ... and those bytes are BGZF blocks (fpl_set_gzip_framing) */
+    bool devBamOut = false;     /* --out *.bam: ... and they are BAM records in BGZF blocks (fpl_set_gzip_records) */
     bool bamKeepArrays = true;  /* a BAM batch's decoded bases are copied back to the host */
     int nFmt = 1, fmtThreads = 1;
     bool splitThreads = false;  /* --split*: the workers' writers have threads of their own */
@@ -284,7 +285,12 @@ void Pipeline::enable_device_gzip() {
     bool eligible = out.fout && out.fout.gz && !out.split && !opt.fragmentMode && !opt.hostGzip && opt.compression <= 4;
     /* --bgzf: under the same conditions the device frames its batches as BGZF blocks; a library without fpl_set_gzip_framing
        makes members only, so the host deflates and frames everything, without a word */
-    if (eligible && opt.bgzf && (in.textMode || (facts.bam && opt.deviceGzip))) eligible = devBgzf = frame_on_all(api.set_gzip_framing, ctxs);
+    /* --out *.bam: the device form under the conditions of a .gz output WITH --device_gzip, for text batches and BAM-backed ones
+       alike (README "BAM output": not the default until whole-run numbers exist); a library without fpl_set_gzip_records leaves
+       everything to the host, without a word.  Records are BGZF by themselves: --bgzf changes nothing for them. */
+    const bool bamOut = out.fout && out.fout.bam;
+    if (bamOut) eligible = eligible && opt.deviceGzip && (in.textMode || facts.bam) && (devBamOut = frame_on_all(api.set_gzip_records, ctxs));
+    if (eligible && !bamOut && opt.bgzf && (in.textMode || (facts.bam && opt.deviceGzip))) eligible = devBgzf = frame_on_all(api.set_gzip_framing, ctxs);
     if (eligible && in.textMode) devGz = enable_on_all(api.set_text_gzip, api.wait_text_gz != nullptr, ctxs);
     /* the same for BAM input (fpl_set_bam_gzip / fpl_wait_bam_gz, C-ABI version 10): the device composes the member from the
        records' names and the bases it decoded, under the same conditions with "parsed on the device" replaced by "BAM-backed
@@ -294,8 +300,11 @@ void Pipeline::enable_device_gzip() {
     if (eligible && facts.bam && opt.deviceGzip) devBamGz = enable_on_all(api.set_bam_gzip, api.wait_bam_gz != nullptr, ctxs);
     bamKeepArrays = !devBamGz || out.ffail; /* (--failed_out is formatted on the host: it needs the decoded bases) */
     devBgzf = devBgzf && (devGz || devBamGz);
-    if ((devGz || devBamGz) && !opt.bgzf && opt.verbose) cerr << "output: gzip members deflated on the device" << endl;
-    if (opt.bgzf && opt.verbose)
+    devBamOut = devBamOut && (devGz || devBamGz);
+    if (bamOut && opt.verbose)
+        cerr << "output: BAM records" << (devBamOut ? ", packed and deflated on the device (a batch that falls back: by the host)" : ", packed and deflated by the host") << endl;
+    if ((devGz || devBamGz) && !opt.bgzf && !bamOut && opt.verbose) cerr << "output: gzip members deflated on the device" << endl;
+    if (opt.bgzf && !bamOut && opt.verbose)
         cerr << "output: BGZF blocks" << (devBgzf ? ", deflated and framed on the device (a batch that falls back: by the host)" : ", deflated and framed by the host") << endl;
 }
 
@@ -417,7 +426,7 @@ class DeviceStage {
     void take_member(Work* w, const uint8_t* gzp, uint64_t gzn) {
         w->gz_member.assign((const char*)gzp, (size_t)gzn);
         w->dev_gz = true;
-        if (p.devBgzf) { /* (BSIZE at byte 16 of every block: the device's blocks all have the 18-byte header) */
+        if (p.devBgzf || p.devBamOut) { /* (BSIZE at byte 16 of every block: the device's blocks all have the 18-byte header) */
             uint64_t blocks = 0;
             for (uint64_t at = 0; at + 18 <= gzn; at += 1u + gzp[at + 16] + 256u * gzp[at + 17]) blocks++;
             p.nDevBgzf += blocks;
@@ -687,8 +696,8 @@ void Pipeline::format_stage(int f) {
             if (w->dev_gz) { /* (formatted for --failed_out alone) */
                 w->outs.resize(1);
                 w->outs[0].swap(w->gz_member);
-            } else if (out.fout && out.fout.gz) out.gzip_pieces(w->outs);
-            if (toFailed && out.ffail.gz) out.gzip_pieces(w->faileds);
+            } else if (out.fout && out.fout.gz) out.gzip_pieces(w->outs, out.fout);
+            if (toFailed && out.ffail.gz) out.gzip_pieces(w->faileds, out.ffail);
         }
         tFormat[(size_t)f] += now_s() - t1;
         doneq.push(w);

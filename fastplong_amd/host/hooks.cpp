@@ -9,6 +9,8 @@
 #include <condition_variable>
 #include <mutex>
 
+#include "bam_out.h"
+#include "../csrc/bam_out_rules.h"
 #include "fastq.h"
 #include "gzip.h"
 #include "pool.h"
@@ -219,6 +221,23 @@ int fplh_bgzf_into(const char* in, uint64_t n, int level, char** out, uint64_t* 
     *out = o.empty() ? nullptr : (char*)malloc(o.size());
     if (*out) memcpy(*out, o.data(), o.size());
     return 0;
+}
+/* test hooks: fplh::fastq_to_bam_records and fplh::bam_header_bytes -> malloc'ed buffers (fplh_free) */
+int fplh_fastq_to_bam_records(const char* in, uint64_t n, char** out, uint64_t* out_len) {
+    std::string s(in ? in : "", (size_t)n), o;
+    fplh::fastq_to_bam_records(s, o);
+    *out_len = o.size();
+    *out = (char*)malloc(o.size() + 1);
+    if (*out) memcpy(*out, o.data(), o.size());
+    return *out ? 0 : -1;
+}
+void fplh_bam_base_table(uint8_t* t) { fpl::bamout::base_table(t); }
+int fplh_bam_header_bytes(char** out, uint64_t* out_len) {
+    const std::string& h = fplh::bam_header_bytes();
+    *out_len = h.size();
+    *out = (char*)malloc(h.size());
+    if (*out) memcpy(*out, h.data(), h.size());
+    return *out ? 0 : -1;
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */

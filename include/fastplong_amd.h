@@ -459,6 +459,26 @@ enum { FPL_GZIP_MEMBER = 0, FPL_GZIP_BGZF = 1 };
 int fpl_set_gzip_framing(fpl_ctx* ctx, int framing);
 
 /*
+ * The form of a gzip batch's bytes.  FPL_ABI_VERSION stays 10: found by symbol lookup like fpl_set_gzip_framing; a caller of a
+ * library without it converts and frames on the host.
+ *
+ *   fpl_set_gzip_records  per context; applies to every kind that can return gzip bytes and takes effect with the NEXT submission,
+ *                      like the framing: a switch with batches in flight is safe.  Other values: FPL_ERR_ARG, and nothing changes.
+ *     FPL_GZIP_FASTQ   (the default) the bytes inflate to FASTQ text, as documented above.
+ *     FPL_GZIP_BAM     the bytes inflate to unaligned BAM records, one per passing fragment in the text's order: block_size, refID
+ *                      -1, pos -1, l_read_name, mapq 0, bin 4680, n_cigar_op 0, flag 4, l_seq, next_refID -1, next_pos -1, tlen
+ *                      0; the name -- the FASTQ name line without its '@' (the split prefix included), cut at the first space or
+ *                      tab, truncated to 254 bytes, "*" when nothing is left -- and its NUL; (l_seq + 1) / 2 bytes of bases in
+ *                      htslib's seq_nt16_table codes, high nibble first; l_seq qualities, max(byte, 33) - 33.  No tags.
+ *                      The framing is BGZF whatever fpl_set_gzip_framing says: a whole number of blocks of 49 152 record bytes
+ *                      each, the last one short, nothing (*gz_len 0) when no read passed; no block is larger than 49 152 + 5 * 68
+ *                      + 31 bytes.  There is no BAM header and no EOF block in them: a file is the caller's header block(s),
+ *                      the batches' bytes in order, and the 28-byte EOF block.
+ */
+enum { FPL_GZIP_FASTQ = 0, FPL_GZIP_BAM = 1 };
+int fpl_set_gzip_records(fpl_ctx* ctx, int records);
+
+/*
  * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
  * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
  * caller then inflates on the host.

@@ -289,6 +289,11 @@ int fpl_set_gzip_framing(fpl_ctx* ctx, int framing) {
     if (!ctx || (framing != FPL_GZIP_MEMBER && framing != FPL_GZIP_BGZF)) return FPL_ERR_ARG;
     return framing == FPL_GZIP_BGZF ? FPL_ERR_NO_DEVICE : FPL_OK;
 }
+/* (nor anything to pack: BAM records are refused like BGZF) */
+int fpl_set_gzip_records(fpl_ctx* ctx, int records) {
+    if (!ctx || (records != FPL_GZIP_FASTQ && records != FPL_GZIP_BAM)) return FPL_ERR_ARG;
+    return records == FPL_GZIP_BAM ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
 /* (BGZF inflate: no device, so no inflater -- a host that finds the calls gets no handle and inflates itself) */
 fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
 int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
