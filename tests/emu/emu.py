@@ -2,28 +2,18 @@
 compiled for the host on a lock-step thread emulator (hip_emu.h)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from fastplong_amd import abi
+from tests import cbuild
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libfpl_emu.so")
-SRCS = [os.path.join(HERE, "emu_driver.cpp"), os.path.join(HERE, "hip_emu.h")] + [
-    os.path.join(ROOT, "fastplong_amd", "csrc", f) for f in ("kernels.h", "pipeline.h", "dev_prims.h", "dev_types.h")
-] + [os.path.join(ROOT, "include", "fastplong_amd.h")]
 
 
 def build():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SRCS):
-        # (into a file of this process's own, then renamed: several pytest-xdist workers may find the library stale at once, and
-        # none of them must load another one's half-written file)
-        tmp = "%s.tmp.%d" % (LIB, os.getpid())
-        subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fPIC", "-shared", "-pthread", "-I" + HERE,
-                               "-o", tmp, SRCS[0]])
-        os.replace(tmp, LIB)
+    return cbuild.emu_lib(LIB, "tests/emu/emu_driver.cpp", __file__)
 
 
 _lib = None

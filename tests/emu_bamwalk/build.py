@@ -14,17 +14,13 @@ one context at a time goes in as a file and the results come out as one:
 Every buffer the kernels see is a heap block of exactly its promised size, so leaving one ends the run with a report."""
 import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests import cbuild, emujob
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 EXE = os.path.join(HERE, "emu_bamwalk_run")
-SRCS = [os.path.join(HERE, "driver.cpp"), os.path.join(ROOT, "tests", "emu", "hip_emu.h")] + [
-    os.path.join(ROOT, "fastplong_amd", "csrc", f) for f in ("bam_walk.h", "bam_rules.h", "dev_prims.h")
-] + [os.path.join(ROOT, "include", "fastplong_amd.h")]
 WINDOW = struct.Struct("<IIQIIQQIIQQ")
 FIELDS = ("status", "n_reads", "n_bases", "max_read_len", "segments", "name_bytes", "records_seen", "tail_bytes", "rewalked", "bad_index",
           "bad_pos")
@@ -32,13 +28,7 @@ NO_CAND = (1 << 64) - 1
 
 
 def build():
-    if not os.path.exists(EXE) or any(os.path.getmtime(s) > os.path.getmtime(EXE) for s in SRCS):
-        tmp = "%s.tmp.%d" % (EXE, os.getpid())
-        subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                               "-fno-sanitize-recover=undefined", "-DEMU_BAMWALK_MAIN", "-pthread", "-I" + os.path.join(ROOT, "tests", "emu"),
-                               "-o", tmp, SRCS[0]])
-        os.replace(tmp, EXE)
-    return EXE
+    return cbuild.emu_program(EXE, "tests/emu_bamwalk/driver.cpp", __file__, main="EMU_BAMWALK_MAIN")
 
 
 def new(tail_cap):
@@ -53,40 +43,16 @@ def run(ops):
     """ops: a list of new() / submit() / ("tail_get",) / ("tail_set", bytes) / ("resume",) / ("reserve", bytes) -> one result per
     submit (a dict: rc, the header's fields, cand, and for an accepted one rec, off, name_off, names) and per tail_get (bytes), in
     order; raises with the sanitizers' report when the run did not end clean"""
-    exe = build()
-    d = tempfile.mkdtemp(prefix="emu_bamwalk_")
-    fin, fout = os.path.join(d, "in"), os.path.join(d, "out")
-    try:
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<Q", len(ops)))
-            for op in ops:
-                if op[0] == "new":
-                    f.write(struct.pack("<QQ", 0, op[1]))
-                elif op[0] == "submit":
-                    _, data, skip, seg, cap, bst = op
-                    f.write(struct.pack("<6Q", 1, len(data), skip, seg, cap, len(bst)) + data + struct.pack("<%dI" % len(bst), *bst))
-                elif op[0] == "tail_get":
-                    f.write(struct.pack("<Q", 2))
-                elif op[0] == "tail_set":
-                    f.write(struct.pack("<QQ", 3, len(op[1])) + bytes(op[1]))
-                elif op[0] == "resume":
-                    f.write(struct.pack("<Q", 4))
-                elif op[0] == "reserve":
-                    f.write(struct.pack("<QQ", 5, op[1]))
-                else:
-                    raise ValueError(op[0])
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        p = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-        if p.returncode != 0:
-            raise RuntimeError("emu_bamwalk_run ended with %d:\n%s" % (p.returncode, p.stdout.decode(errors="replace")[-4000:]))
-        raw = open(fout, "rb").read()
-    finally:
-        for f in ("in", "out"):
-            try:
-                os.unlink(os.path.join(d, f))
-            except OSError:
-                pass
-        os.rmdir(d)
+    def payload(f):
+        f.write(struct.pack("<Q", len(ops)))
+        for op in ops:
+            if op[0] == "submit":
+                _, data, skip, seg, cap, bst = op
+                f.write(struct.pack("<6Q", 1, len(data), skip, seg, cap, len(bst)) + data + struct.pack("<%dI" % len(bst), *bst))
+            elif not emujob.write_context_op(f, op):
+                raise ValueError(op[0])
+
+    raw = emujob.run(build(), payload, "emu_bamwalk_")
     res, at = [], 0
     for op in ops:
         if op[0] == "submit":

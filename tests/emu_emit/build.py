@@ -1,27 +1,18 @@
 """TEST INFRASTRUCTURE ONLY -- builds tests/emu_emit/libfpl_emu_emit.so: the emit kernels on the host (tests/emu/hip_emu.h)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from fastplong_amd import abi
+from tests import cbuild
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libfpl_emu_emit.so")
-SRCS = [os.path.join(HERE, "driver.cpp"), os.path.join(ROOT, "tests", "emu", "hip_emu.h"),
-        os.path.join(ROOT, "fastplong_amd", "csrc", "emit.h"), os.path.join(ROOT, "fastplong_amd", "csrc", "dev_prims.h"),
-        os.path.join(ROOT, "include", "fastplong_amd.h")]
 
 
 def build():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SRCS):
-        tmp = "%s.tmp.%d" % (LIB, os.getpid())
-        subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "tests", "emu"),
-                               "-o", tmp, SRCS[0]])
-        os.replace(tmp, LIB)
-    return LIB
+    return cbuild.emu_lib(LIB, "tests/emu_emit/driver.cpp", __file__)
 
 
 _lib = None

@@ -17,17 +17,13 @@ A script of operations on one context at a time goes in as a file and the result
 Every buffer the kernels see is a heap block of exactly its promised size, so leaving one ends the run with a report."""
 import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests import cbuild, emujob
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 EXE = os.path.join(HERE, "emu_textwalk_run")
-SRCS = [os.path.join(HERE, "driver.cpp"), os.path.join(ROOT, "tests", "emu", "hip_emu.h")] + [
-    os.path.join(ROOT, "fastplong_amd", "csrc", f) for f in ("text_walk.h", "text_parse.h", "bam_walk.h", "bam_rules.h", "dev_prims.h")
-] + [os.path.join(ROOT, "include", "fastplong_amd.h")]
 WINDOW = struct.Struct("<IIQIIQQIIQQ")
 FIELDS = ("status", "n_reads", "n_bases", "max_read_len", "n_lines", "name_bytes", "records_seen", "tail_bytes", "reserved", "bad_index",
           "bad_pos")
@@ -37,13 +33,7 @@ NONE = (1 << 64) - 1
 
 
 def build():
-    if not os.path.exists(EXE) or any(os.path.getmtime(s) > os.path.getmtime(EXE) for s in SRCS):
-        tmp = "%s.tmp.%d" % (EXE, os.getpid())
-        subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                               "-fno-sanitize-recover=undefined", "-DEMU_TEXTWALK_MAIN", "-pthread", "-I" + os.path.join(ROOT, "tests", "emu"),
-                               "-o", tmp, SRCS[0]])
-        os.replace(tmp, EXE)
-    return EXE
+    return cbuild.emu_program(EXE, "tests/emu_textwalk/driver.cpp", __file__, main="EMU_TEXTWALK_MAIN")
 
 
 def new(tail_cap):
@@ -68,42 +58,18 @@ def run(ops):
     result per submit (a dict: rc, lo, the header's fields, and for an accepted one line, len, off, name_off, names, seq, qual), per
     whole (a dict: the TextHeader's fields, and for status 0 line, len, off, seq, qual) and per tail_get (bytes), in order; raises
     with the sanitizers' report when the run did not end clean"""
-    exe = build()
-    d = tempfile.mkdtemp(prefix="emu_textwalk_")
-    fin, fout = os.path.join(d, "in"), os.path.join(d, "out")
-    try:
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<Q", len(ops)))
-            for op in ops:
-                if op[0] == "new":
-                    f.write(struct.pack("<QQ", 0, op[1]))
-                elif op[0] == "submit":
-                    _, data, bst = op
-                    f.write(struct.pack("<3Q", 1, len(data), len(bst)) + data + struct.pack("<%dI" % len(bst), *bst))
-                elif op[0] == "tail_get":
-                    f.write(struct.pack("<Q", 2))
-                elif op[0] == "tail_set":
-                    f.write(struct.pack("<QQ", 3, len(op[1])) + bytes(op[1]))
-                elif op[0] == "resume":
-                    f.write(struct.pack("<Q", 4))
-                elif op[0] == "reserve":
-                    f.write(struct.pack("<QQ", 5, op[1]))
-                elif op[0] == "whole":
-                    f.write(struct.pack("<QQ", 6, len(op[1])) + op[1])
-                else:
-                    raise ValueError(op[0])
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        p = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
-        if p.returncode != 0:
-            raise RuntimeError("emu_textwalk_run ended with %d:\n%s" % (p.returncode, p.stdout.decode(errors="replace")[-4000:]))
-        raw = open(fout, "rb").read()
-    finally:
-        for f in ("in", "out"):
-            try:
-                os.unlink(os.path.join(d, f))
-            except OSError:
-                pass
-        os.rmdir(d)
+    def payload(f):
+        f.write(struct.pack("<Q", len(ops)))
+        for op in ops:
+            if op[0] == "submit":
+                _, data, bst = op
+                f.write(struct.pack("<3Q", 1, len(data), len(bst)) + data + struct.pack("<%dI" % len(bst), *bst))
+            elif op[0] == "whole":
+                f.write(struct.pack("<QQ", 6, len(op[1])) + op[1])
+            elif not emujob.write_context_op(f, op):
+                raise ValueError(op[0])
+
+    raw = emujob.run(build(), payload, "emu_textwalk_")
     res, at = [], 0
     for op in ops:
         if op[0] == "submit":
