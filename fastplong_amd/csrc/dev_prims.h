@@ -284,6 +284,15 @@ __device__ __forceinline__ void dot_settle(u32& a, u32& b) {
     (void)b;
 #endif
 }
+__device__ __forceinline__ void dot_settle(u32& a, u32& b, u32& c) {
+#ifndef FPL_EMU
+    asm volatile("s_nop 3" : "+v"(a), "+v"(b), "+v"(c));
+#else
+    (void)a;
+    (void)b;
+    (void)c;
+#endif
+}
 /* sum of the 4 bytes of a, plus c (v_sad_u8 against 0) */
 __device__ __forceinline__ u32 sum_bytes(u32 a, u32 c) {
 #ifdef FPL_EMU

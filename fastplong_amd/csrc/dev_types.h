@@ -43,6 +43,9 @@ struct DevAdapter {
        pattern is the first 16 columns */
     uint32_t peq4_e32[4];
     uint32_t peq4_s32r[4];
+    /* term[] for the lane-per-read window scans (k_trim_ends_batched, ham_scan_lanes), where the plane words of a lane lie a slot
+       apart and not a lane apart: (4 * code * 64) << 8 | (i & 31) -- which word base i starts in is the caller's to add */
+    uint32_t term_own[64];
 };
 
 /* Options as the kernels consume them: integers only. */
@@ -86,12 +89,13 @@ inline void build_adapter(DevAdapter* a, const char* seq, int len) {
         a->peq_full[c][i >> 6] |= 1ull << (i & 63);
     }
     a->acgt_only = len <= 64;
-    for (int i = 0; i < 64; i++) a->term[i] = (4u * 4u * 64u) << 8; /* padding: the all-zero plane row */
+    for (int i = 0; i < 64; i++) a->term[i] = a->term_own[i] = (4u * 4u * 64u) << 8; /* padding: the all-zero plane row */
     for (int i = 0; i < len && i < 64; i++) {
         const uint8_t c = (uint8_t)seq[i];
         if (c != 'A' && c != 'C' && c != 'G' && c != 'T') a->acgt_only = 0;
         const uint32_t code = (c >> 1) & 3u; /* A0 C1 T2 G3 */
         a->term[i] = ((4u * (code * 64u + (uint32_t)(i >> 5))) << 8) | (uint32_t)(i & 31);
+        a->term_own[i] = ((4u * code * 64u) << 8) | (uint32_t)(i & 31);
     }
     for (int i = 0; i < len && i < 64; i++) {
         const uint8_t c = (uint8_t)seq[i];

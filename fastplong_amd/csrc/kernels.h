@@ -1779,95 +1779,30 @@ __device__ __forceinline__ int trim_polyx_lanes(const u8* __restrict__ r, int rl
     return rlen - p2 - 1; /* Read::resize: a no-op when pos == -1 */
 }
 
-/* the four bases of a dword as one-hot nibbles (A 1, C 2, G 4, T 8; any other byte 0), base k in bits 4k..4k+3 */
-__device__ __forceinline__ u32 onehot4(u32 w) {
-    const u32 code = (w >> 1) & 0x03030303u;            /* A0 C1 T2 G3 */
-    const u32 t = perm_lo(0x47544341u, code) ^ w;       /* zero byte <=> exactly that letter */
-    const u32 ok = (~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) >> 7) & 0x01010101u;
-    const u32 nib = perm_lo(0x04080201u, code) & (ok * 15u);
-    const u32 h = (nib | (nib >> 4)) & 0x00FF00FFu;
-    return (h | (h >> 8)) & 0xFFFFu;
-}
-/* searchAdapter's window scan (src/adaptertrimmer.cpp:84-131) with LANE = READ: every lane slides a 32-base window of one-hot
- * nibbles along its own read -- four bases enter per dword load -- and counts the adapter's matches with four AND + popcount.
+/* searchAdapter's window scan (src/adaptertrimmer.cpp:84-131) with LANE = READ, bit-sliced: a lane's window (the first
+ * min(rlen, 200) bases of r1 at the START, the last 200 at the end) is seven words of letter bit-planes of its own, position p
+ * = bit p % 32 of word p / 32, and the adapter's matches at 32 positions are counted at once as k_scan counts them
+ * (match_counts: one v_alignbit per adapter base, Harley-Seal adders) -- 3 to 4 vector instructions per adapter base and 32
+ * positions where a sliding window of one-hot nibbles took 24 per position.  No word crosses lanes.
  * r1 / rlen: this lane's trimmed read.  START: asRightAsPossible over p in [0, min(rlen, 200) - alen]: hit = the LARGEST p
  * within thr (the reference scans downwards and returns at once), else cand = the smallest p among the minima (ties: "<="
  * in a descending scan).  END: asLeftAsPossible over p in [max(0, rlen - 200), rlen - alen): hit = the SMALLEST p within thr,
- * else cand = the largest p among the minima.  hit / cand are -1 when there is none.  A few hundred vector instructions per
- * 64 reads and end where the scan with lanes = positions (one read at a time) took as many per read. */
-/* NW: words of one-hot nibbles the window holds -- 4 for adapters of <= 32 bases, 8 for <= 64 */
+ * else cand = the largest p among the minima.  hit / cand are -1 when there is none.
+ * NW: 4 for adapters of <= 32 bases (two plane words per output word, six count planes), 8 for <= 64 (three and seven).
+ * Defined behind match_counts / sliced_max. */
+/* Where a wave parks the plane words its lanes are counting on, [slot][letter row A C T G, row 4 all zero][lane]: the row stride
+   of 64 words is the one DevAdapter::term[] encodes, and ds_read_addtid fetches a lane's own word of any row.  Only the words an
+   output word needs are held: word w lies in slot w % RING, and slot RING repeats slot 0, so that the word behind the one in
+   slot RING - 1 is one slot further too (the second word of a term is a fixed byte offset behind its first). */
+template <int NW>
+struct HamScanPark {
+    static constexpr int RING = NW <= 4 ? 2 : 3;
+    u32 w[RING + 1][5][64];
+};
 template <bool START, int NW = 4>
-__device__ __forceinline__ void ham_scan_lanes(const u8* __restrict__ r1, int rlen, bool active, const u32 (&ad1h)[NW], int alen,
-                                               int thr, const u8* __restrict__ seq_end, int& hit, int& cand) {
-    hit = -1;
-    cand = -1;
-    int p_lo = 0, np = 0; /* first position and number of positions of this lane */
-    if (START) {
-        const int searchEnd = min(rlen, FPL_END_WINDOW);
-        if (active && alen <= rlen && searchEnd > alen) np = searchEnd - alen + 1;
-    } else {
-        const int ss = max(0, rlen - FPL_END_WINDOW);
-        if (active && ss + alen <= rlen) {
-            p_lo = ss;
-            np = rlen - alen - ss; /* the last position is never tested */
-        }
-    }
-    const int npmax = (int)wave_max_u32((u32)max(np, 0));
-    if (npmax == 0) return; /* wave-uniform */
-    const u8* base = r1 + p_lo;
-    const int navail = np > 0 ? rlen - p_lo : 0; /* bytes of the read from `base` on */
-    /* dword k of the stream: bases 4k .. 4k + 3 behind `base`; bytes past the read count as no base */
-    auto nibbles = [&](int k) -> u32 {
-        const int left = navail - 4 * k;
-        if (left <= 0) return 0u;
-        u32 w = load4_guard(base + 4 * k, seq_end);
-        if (left < 4) w &= (1u << (8 * left)) - 1u;
-        return onehot4(w);
-    };
-    u32 touch = 0;
-    if (navail > 64) /* the window's second (and third) cache line, asked for now */
-        touch = (u32)*(base + min(navail - 1, 112)) + (u32)*(base + min(navail - 1, 207));
-    u32 W[NW];
-#pragma unroll
-    for (int k = 0; k < NW; k++) W[k] = nibbles(2 * k) | (nibbles(2 * k + 1) << 16);
-    int bestmm = 0x7fffffff;
-    u32 nxt = nibbles(2 * NW);
-    for (int i0 = 0; i0 < npmax; i0 += 4) { /* wave-uniform trip count */
-        const u32 cur = nxt;
-        nxt = nibbles(i0 / 4 + 2 * NW + 1); /* (requested one step ahead of its use) */
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int i = i0 + u;
-            u32 matches = popc32(W[0] & ad1h[0]);
-#pragma unroll
-            for (int k = 1; k < NW; k++) matches = popc_acc(W[k] & ad1h[k], matches);
-            const int mm = alen - (int)matches;
-            const bool in = i < np;
-            const int p = p_lo + i;
-            if (START) {
-                hit = (in && mm <= thr) ? p : hit;         /* ascending: the last one stands */
-                const bool better = in && mm < bestmm;     /* the first of the minima */
-                cand = better ? p : cand;
-                bestmm = better ? mm : bestmm;
-            } else {
-                hit = (in && hit < 0 && mm <= thr) ? p : hit; /* the first one stands */
-                const bool better = in && mm <= bestmm;       /* the last of the minima */
-                cand = better ? p : cand;
-                bestmm = better ? mm : bestmm;
-            }
-            /* slide by one base: the next nibble of the stream enters at the top */
-#pragma unroll
-            for (int k = 0; k + 1 < NW; k++) W[k] = alignbit(W[k + 1], W[k], 4);
-            W[NW - 1] = (W[NW - 1] >> 4) | (((cur >> (4 * u)) & 15u) << 28);
-        }
-    }
-    if (hit >= 0) cand = -1;
-#if !defined(FPL_EMU)
-    asm volatile("" ::"v"(touch));
-#else
-    (void)touch;
-#endif
-}
+__device__ __forceinline__ void ham_scan_lanes(const u8* __restrict__ r1, int rlen, bool active, const DevAdapter* __restrict__ ad,
+                                               int alen, int thr, const u8* __restrict__ seq_end, HamScanPark<NW>& park, int& hit,
+                                               int& cand);
 
 /* Global edit distance <= thr? between the adapter slice [shift, shift + m) (m <= 32; peqf = word 0 of the adapter's Peq
  * table, in LDS) and the m text bytes at `text`, one problem per lane (need = this lane has one).  The exact distance
@@ -2112,11 +2047,13 @@ __device__ __forceinline__ int lane_get(int v, int j) { return readlane_i32(v, j
 __device__ __forceinline__ void lane_set(int& v, int j, int x) { v = lane_id() == j ? x : v; }
 
 #ifndef FPL_TRIM_WAVES_PER_SIMD_BATCHED
-#define FPL_TRIM_WAVES_PER_SIMD_BATCHED 5 /* (the lane-per-read phases hold a read's state and a sliding window per lane: 72 registers
-                                             spilled 51 of them -- 1.80 ms per million reads at 7 waves per SIMD, 1.55 at 6, 1.48 at 5) */
+#define FPL_TRIM_WAVES_PER_SIMD_BATCHED 5 /* (the lane-per-read phases hold a read's state and the words of a scan per lane: 72 registers
+                                             spilled 51 of them -- 1.80 ms per million reads at 7 waves per SIMD, 1.55 at 6, 1.48 at 5;
+                                             five also need the block's LDS within 32 KiB: see WaveLds in the kernel) */
 #endif
-/* NW: words of one-hot nibbles per window scan -- 4: both command-line adapters have <= 32 bases (DevConfig::trim_mode 1), 8: <= 64
-   (trim_mode 2).  CHAIN: a FASTA chain follows (k_trim_ends<.., 2> with `pre` = the ReadState records written here): the bases the
+/* NW: 4: both command-line adapters have <= 32 bases (DevConfig::trim_mode 1), 8: <= 64 (trim_mode 2) -- the plane words and count
+   planes of the window scans (ham_scan_lanes), the width of the confirmations (lev_lanes_nw).
+   CHAIN: a FASTA chain follows (k_trim_ends<.., 2> with `pre` = the ReadState records written here): the bases the
    two command-line adapters took ride along in ReadState::pad and FilterResult::addReadTrimmed is left to the chain kernel, which
    knows the read's total (src/seprocessor.cpp:205-216) */
 template <int WAVES, int NW = 4, bool CHAIN = false>
@@ -2125,12 +2062,28 @@ k_trim_ends_batched(const u8* __restrict__ seq, const u8* __restrict__ qual, con
                     uint64_t n_bytes, const DevConfig* __restrict__ cfg, const DevAdapter* __restrict__ ads,
                     ReadState* __restrict__ state, long long* __restrict__ counters, u32 C, u32* __restrict__ group_ctr) {
     __shared__ TrimBlockAcc acc;
-    __shared__ TrimLds<WAVES> lds;
+    /* the two adapters' tables (TrimLds): [0] = start adapter's peq16_start, [1] = end adapter's peq16_end; word 0 of the full tables */
+    struct AdapterLds {
+        uint16_t peq16[2][256];
+        uint64_t peqf[2][256][1];
+    };
+    __shared__ AdapterLds lds;
     __shared__ int thr_lds[72]; /* DevConfig::thr[0..64] */
-    __shared__ u32 cand_lds[WAVES][PART_WORDS][64]; /* per lane: the columns its partial-pattern search may end at */
+    /* per wave, one after the other and never at once: the plane words of a window scan (lane = read) | per lane, the columns its
+       partial-pattern search may end at, and the windows of the read that takes a wave-per-read step (TrimLds::win / win4) */
+    union WaveLds {
+        HamScanPark<NW> park;
+        struct {
+            u32 cand[PART_WORDS][64];
+            u32 win[4][TRIM_WIN / 4 + 8];
+            u32 win4[2][TRIM_WIN / 8 + 8];
+        } rd;
+    };
+    __shared__ WaveLds wave_lds[WAVES];
     PROF_INIT();
     const int lane = lane_id();
-    u32(*const cand)[64] = cand_lds[wave_in_block()];
+    u32(*const cand)[64] = wave_lds[wave_in_block()].rd.cand;
+    HamScanPark<NW>& park = wave_lds[wave_in_block()].park;
     for (u32 i = threadIdx.x; i < FPL_FR_LEN; i += blockDim.x) acc.fr[i] = 0;
     for (u32 i = threadIdx.x; i < 2 * 2 * FPL_KEY_STRIDE; i += blockDim.x) acc.key[i] = 0;
     for (u32 i = threadIdx.x; i < 256; i += blockDim.x) {
@@ -2143,24 +2096,18 @@ k_trim_ends_batched(const u8* __restrict__ seq, const u8* __restrict__ qual, con
     __syncthreads();
     const u8* seq_end = seq + n_bytes;
     const u8* qual_end = qual + n_bytes;
-    u32* const win_s = lds.win[wave_in_block()][0];
-    u32* const win_e = lds.win[wave_in_block()][1];
-    u32* const win_hq = lds.win[wave_in_block()][2];
-    u32* const win_tq = lds.win[wave_in_block()][3];
-    u32* const win4_s = lds.win4[wave_in_block()][0];
-    u32* const win4_e = lds.win4[wave_in_block()][1];
+    u32* const win_s = wave_lds[wave_in_block()].rd.win[0];
+    u32* const win_e = wave_lds[wave_in_block()].rd.win[1];
+    u32* const win_hq = wave_lds[wave_in_block()].rd.win[2];
+    u32* const win_tq = wave_lds[wave_in_block()].rd.win[3];
+    u32* const win4_s = wave_lds[wave_in_block()].rd.win4[0];
+    u32* const win4_e = wave_lds[wave_in_block()].rd.win4[1];
     const bool do_ad = cfg->adapter_enabled != 0;
     const bool do_start = do_ad && cfg->has_start, do_end = do_ad && cfg->has_end;
     const int ext = cfg->ext;
     const int alen0 = ads[0].len, alen1 = ads[1].len;
     constexpr int plen = FPL_PATTERN_LEN; /* (both adapters have >= 16 bases here) */
     const int thrA0 = cfg->thr[alen0], thrA1 = cfg->thr[alen1], thrP = cfg->thr[plen];
-    u32 ad1h0[NW], ad1h1[NW];
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        ad1h0[k] = uniform_u32(ads[0].onehot[k]);
-        ad1h1[k] = uniform_u32(ads[1].onehot[k]);
-    }
 
     /* groups of 64 reads are handed out through one counter (zeroed before the batch): the grid is what the chip holds
        at once, and no wave idles while another still has rounds to go */
@@ -2242,7 +2189,7 @@ k_trim_ends_batched(const u8* __restrict__ seq, const u8* __restrict__ qual, con
         /* ---- P1c: start adapter window scan, lane = read (searchAdapter, asRightAsPossible, :109-131) */
         if (do_start) {
             const bool act = v_alive && (v_e - v_s) >= FPL_PATTERN_LEN;
-            ham_scan_lanes<true, NW>(seq + v_o0 + v_s, v_e - v_s, act, ad1h0, alen0, thrA0, seq_end, v_mpos, v_cand);
+            ham_scan_lanes<true, NW>(seq + v_o0 + v_s, v_e - v_s, act, &ads[0], alen0, thrA0, seq_end, park, v_mpos, v_cand);
         }
         PROF(3) /* window scan, start */
         /* ---- P2: the candidates' edit distance, 64 reads at once */
@@ -2332,7 +2279,7 @@ k_trim_ends_batched(const u8* __restrict__ seq, const u8* __restrict__ qual, con
         v_cand = -1;
         if (do_end) {
             const bool act = v_alive && (v_e - v_s) >= FPL_PATTERN_LEN;
-            ham_scan_lanes<false, NW>(seq + v_o0 + v_s, v_e - v_s, act, ad1h1, alen1, thrA1, seq_end, v_mpos, v_cand);
+            ham_scan_lanes<false, NW>(seq + v_o0 + v_s, v_e - v_s, act, &ads[1], alen1, thrA1, seq_end, park, v_mpos, v_cand);
         }
         PROF(7) /* window scan, end */
         /* ---- P6 */
@@ -2451,9 +2398,11 @@ k_trim_ends_batched(const u8* __restrict__ seq, const u8* __restrict__ qual, con
     __syncthreads();
     long long* fr = counters + FPL_OFF_FR(C);
     long long* keyh = counters + FPL_OFF_KEYHIST(C);
-    for (u32 i = threadIdx.x; i < FPL_FR_LEN; i += blockDim.x)
+    u32 tid = threadIdx.x;
+    opaque_u32(tid); /* (the addresses of the flush are worked out here, not in front of the loop and held in registers all through it) */
+    for (u32 i = tid; i < FPL_FR_LEN; i += blockDim.x)
         if (acc.fr[i]) atomicAdd((u64*)&fr[i], acc.fr[i]);
-    for (u32 i = threadIdx.x; i < 2 * 2 * FPL_KEY_STRIDE; i += blockDim.x)
+    for (u32 i = tid; i < 2 * 2 * FPL_KEY_STRIDE; i += blockDim.x)
         if (acc.key[i]) atomicAdd((u64*)&keyh[i], (u64)acc.key[i]);
 }
 
@@ -3135,6 +3084,8 @@ __device__ inline void range_scan_bytes(const u8* __restrict__ rb, const u8* __r
  * v_dot4_u32_u8 against power-of-two weights: 4 bases per instruction and plane. */
 /* three bit-planes of 32 bases that are all exactly A, C, G, T or N: bit j of L / H / N = ASCII bit 1 / 2 / 3 of base j
    (A 000, C 001 -- L set --, T 010, G 011; bit 3 is set for N = 0x4E alone, whose L and H bits read like G's) */
+/* SETTLE: wait out the dot products before their sums are read (dot_settle), wherever the scheduler puts what follows */
+template <bool SETTLE = false>
 __device__ __forceinline__ void code_planes(const u32 s[8], u32& L, u32& H, u32& N) {
     /* the masked bit itself is the multiplicand (2, 4 or 8 per base instead of 1): no shift per dword and plane */
     L = 0;
@@ -3151,11 +3102,19 @@ __device__ __forceinline__ void code_planes(const u32 s[8], u32& L, u32& H, u32&
             hb = udot4(w & 0x04040404u, wt, hb);
             nb = udot4(w & 0x08080808u, wt, nb);
         }
+        if (SETTLE) dot_settle(lb, hb, nb);
         /* lb = 2 * (8 plane bits), hb = 4 * ..., nb = 8 * ...: the factor goes away with the shift that parks the byte */
         L |= pr ? lb << (8 * pr - 1) : lb >> 1;
         H |= pr ? hb << (8 * pr - 2) : hb >> 2;
         N |= pr ? nb << (8 * pr - 3) : nb >> 3;
     }
+}
+/* the four letter planes of 32 such bases out of their code planes */
+__device__ __forceinline__ void letter_planes(u32 cL, u32 cH, u32 cN, u32& PA, u32& PC, u32& PT, u32& PG) {
+    PA = ~(cH | cL); /* (an N has both bits set) */
+    PC = ~cH & cL;
+    PT = cH & ~cL;
+    PG = cH & cL & ~cN;
 }
 /* non-zero when one of the 32 bytes is not exactly A, C, G, T or N: ASCII bits 1..3 pick the letter the byte would have
    to be out of a table (codes 4..6 pick a zero byte, which no base is) */
@@ -3192,6 +3151,7 @@ __device__ __forceinline__ void sums32_acgtn(const u32 s0, const u32 q[8], int n
     const u32 d0 = ((s0 & 0xFFu) != (prev_dword >> 24)) ? 1u : 0u;
     diff = popc_acc(dm, diff) + d0;
 }
+template <bool SETTLE = false>
 __device__ __forceinline__ void build_planes(const u32 s[8], u32& PA, u32& PC, u32& PT, u32& PG) {
     u32 L = 0, H = 0, X = 0;
 #pragma unroll
@@ -3209,6 +3169,7 @@ __device__ __forceinline__ void build_planes(const u32 s[8], u32& PA, u32& PC, u
             const u32 nz = ((((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) >> 7) & 0x01010101u;
             xb = udot4(nz, wt, xb);
         }
+        if (SETTLE) dot_settle(lb, hb, xb);
         L |= lb << (8 * pr);
         H |= hb << (8 * pr);
         X |= xb << (8 * pr);
@@ -3223,13 +3184,17 @@ __device__ __forceinline__ void build_planes(const u32 s[8], u32& PA, u32& PC, u
 /* Number of adapter bases that match at each of this lane's 32 positions, as 7 bit-planes
  * (count <= 64).  plane_lane = &planes[0][lane] in LDS; term i fetches the plane of adapter letter
  * i shifted by i positions (two neighbouring words + v_alignbit); Harley-Seal carry-save adders
- * (v_bitop3 majority / parity) sum eight 1-bit planes with seven CSAs. */
-template <int NB>
-__device__ __forceinline__ void match_counts(const u32* __restrict__ plane_lane, const DevAdapter* __restrict__ ad, u32 (&B)[NB]) {
+ * (v_bitop3 majority / parity) sum eight 1-bit planes with seven CSAs.
+ * HI_OFF: bytes from a term's first word to its second -- 4 in k_scan, where the next 32 positions are the next lane's; a whole
+ * slot in ham_scan_lanes, where they are the same lane's next plane word (OWN: DevAdapter::term_own, which leaves the word a
+ * base starts in to adj32 -- wave-uniform, bytes, added to the plane address of the terms of adapter bases 32..63). */
+template <int NB, int HI_OFF = 4, bool OWN = false>
+__device__ __forceinline__ void match_counts(const u32* __restrict__ plane_lane, const DevAdapter* __restrict__ ad, u32 (&B)[NB],
+                                             int adj32 = 0) {
     const int alen = ad->len;
 #ifndef FPL_EMU
     /* LDS byte address of lane 0's plane word, minus what the instruction adds for this lane */
-    const u32 planes_m0 = uniform_u32((u32)(size_t)plane_lane - 4u * (u32)lane_id());
+    const u32 planes_m0_lo = uniform_u32((u32)(size_t)plane_lane - 4u * (u32)lane_id());
 #endif
 #pragma unroll
     for (int b = 0; b < NB; b++) B[b] = 0;
@@ -3237,32 +3202,33 @@ __device__ __forceinline__ void match_counts(const u32* __restrict__ plane_lane,
     auto group8 = [&](int i0) -> u32 {
         u32 m[8], tw[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) tw[k] = ad->term[i0 + k]; /* terms past alen point at the all-zero plane row */
+        for (int k = 0; k < 8; k++) tw[k] = OWN ? ad->term_own[i0 + k] : ad->term[i0 + k]; /* terms past alen point at the all-zero plane row */
 #ifdef FPL_EMU
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const u32* p = plane_lane + (tw[k] >> 10);
-            m[k] = alignbit(p[1], p[0], tw[k] & 31u);
+            const u32* p = plane_lane + (tw[k] >> 10) + (i0 >= 32 ? adj32 / 4 : 0);
+            m[k] = alignbit(p[HI_OFF / 4], p[0], tw[k] & 31u);
         }
 #else
         /* ds_read_addtid_b32: LDS address = M0 + offset + 4 * lane, so a term costs two scalar ops and no
            address arithmetic on the vector unit (the compiler has no intrinsic for it) */
         u32 lo[8], hi[8], m0_keep;
+        const u32 planes_m0 = planes_m0_lo + (u32)(i0 >= 32 ? adj32 : 0);
         asm volatile(
             "s_mov_b32 %16, m0\n"
-            "s_lshr_b32 m0, %17, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %0 offset:0\n ds_read_addtid_b32 %8 offset:4\n"
-            "s_lshr_b32 m0, %18, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %1 offset:0\n ds_read_addtid_b32 %9 offset:4\n"
-            "s_lshr_b32 m0, %19, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %2 offset:0\n ds_read_addtid_b32 %10 offset:4\n"
-            "s_lshr_b32 m0, %20, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %3 offset:0\n ds_read_addtid_b32 %11 offset:4\n"
-            "s_lshr_b32 m0, %21, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %4 offset:0\n ds_read_addtid_b32 %12 offset:4\n"
-            "s_lshr_b32 m0, %22, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %5 offset:0\n ds_read_addtid_b32 %13 offset:4\n"
-            "s_lshr_b32 m0, %23, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %6 offset:0\n ds_read_addtid_b32 %14 offset:4\n"
-            "s_lshr_b32 m0, %24, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %7 offset:0\n ds_read_addtid_b32 %15 offset:4\n"
+            "s_lshr_b32 m0, %17, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %0 offset:0\n ds_read_addtid_b32 %8 offset:%26\n"
+            "s_lshr_b32 m0, %18, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %1 offset:0\n ds_read_addtid_b32 %9 offset:%26\n"
+            "s_lshr_b32 m0, %19, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %2 offset:0\n ds_read_addtid_b32 %10 offset:%26\n"
+            "s_lshr_b32 m0, %20, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %3 offset:0\n ds_read_addtid_b32 %11 offset:%26\n"
+            "s_lshr_b32 m0, %21, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %4 offset:0\n ds_read_addtid_b32 %12 offset:%26\n"
+            "s_lshr_b32 m0, %22, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %5 offset:0\n ds_read_addtid_b32 %13 offset:%26\n"
+            "s_lshr_b32 m0, %23, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %6 offset:0\n ds_read_addtid_b32 %14 offset:%26\n"
+            "s_lshr_b32 m0, %24, 8\n s_add_u32 m0, m0, %25\n s_nop 0\n ds_read_addtid_b32 %7 offset:0\n ds_read_addtid_b32 %15 offset:%26\n"
             "s_waitcnt lgkmcnt(0)\n s_mov_b32 m0, %16"
             : "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(lo[4]), "=&v"(lo[5]), "=&v"(lo[6]), "=&v"(lo[7]),
               "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4]), "=&v"(hi[5]), "=&v"(hi[6]), "=&v"(hi[7]),
               "=&s"(m0_keep)
-            : "s"(tw[0]), "s"(tw[1]), "s"(tw[2]), "s"(tw[3]), "s"(tw[4]), "s"(tw[5]), "s"(tw[6]), "s"(tw[7]), "s"(planes_m0)
+            : "s"(tw[0]), "s"(tw[1]), "s"(tw[2]), "s"(tw[3]), "s"(tw[4]), "s"(tw[5]), "s"(tw[6]), "s"(tw[7]), "s"(planes_m0), "n"(HI_OFF)
             : "scc", "memory"); /* M0 is restored: the compiler does not know it was touched */
         (void)m0_keep;
 #pragma unroll
@@ -3299,8 +3265,8 @@ __device__ __forceinline__ void match_counts(const u32* __restrict__ plane_lane,
     for (; i0 < alen; i0 += 8) ripple(group8(i0), 3);
 }
 
-/* largest count among the positions in `cand` (non-zero) and the first position holding it */
-template <int NB>
+/* largest count among the positions in `cand` (non-zero) and the first position holding it (LAST: the last one) */
+template <int NB, bool LAST = false>
 __device__ __forceinline__ void sliced_max(const u32 (&B)[NB], u32 cand, int& val, int& first) {
     val = 0;
 #pragma unroll
@@ -3319,6 +3285,133 @@ __device__ __forceinline__ void sliced_max(const u32 (&B)[NB], u32 cand, int& va
 #endif
     }
     first = __ffs(cand) - 1;
+    if (LAST) first = 31 - (int)__clz((int)cand);
+}
+/* the positions whose count is at least t (wave-uniform, 1 <= t < 2^NB) */
+template <int NB>
+__device__ __forceinline__ u32 sliced_ge(const u32 (&B)[NB], int t) {
+    const u32 k = (1u << NB) - (u32)t; /* count + k carries out of the NB planes <=> count >= t */
+    u32 c = 0;
+#pragma unroll
+    for (int b = 0; b < NB; b++) c = bitop3<0xE8>(B[b], c, ((k >> b) & 1u) ? ~0u : 0u); /* the carry of a full adder: the majority */
+    return c;
+}
+
+/* ham_scan_lanes: see its declaration in front of k_trim_ends_batched */
+template <bool START, int NW>
+__device__ __forceinline__ void ham_scan_lanes(const u8* __restrict__ r1, int rlen, bool active, const DevAdapter* __restrict__ ad,
+                                               int alen, int thr, const u8* __restrict__ seq_end, HamScanPark<NW>& park, int& hit,
+                                               int& cand) {
+    constexpr int NB = NW <= 4 ? 6 : 7;             /* count planes: matches <= 32 / <= 64 */
+    constexpr int RING = HamScanPark<NW>::RING;     /* plane words an output word needs: its own and one (two) behind it */
+    constexpr int SLOT = (int)sizeof(park.w[0]);    /* bytes */
+    constexpr int NWORDS = (FPL_END_WINDOW + 31) / 32;
+    hit = -1;
+    cand = -1;
+    int p_lo = 0, np = 0; /* first position and number of positions of this lane */
+    int navail = 0;       /* bases of the window from p_lo on */
+    if (START) {
+        const int searchEnd = min(rlen, FPL_END_WINDOW);
+        if (active && alen <= rlen && searchEnd > alen) {
+            np = searchEnd - alen + 1;
+            navail = searchEnd;
+        }
+    } else {
+        const int ss = max(0, rlen - FPL_END_WINDOW);
+        if (active && ss + alen <= rlen) {
+            p_lo = ss;
+            np = rlen - alen - ss; /* the last position is never tested */
+            navail = np > 0 ? rlen - ss : 0;
+        }
+    }
+    const int npmax = (int)wave_max_u32((u32)max(np, 0));
+    if (npmax == 0) return; /* wave-uniform */
+    const int nwo = (npmax + 31) >> 5;                                          /* output words */
+    const int nww = min(NWORDS, ((int)wave_max_u32((u32)navail) + 31) >> 5);     /* plane words that hold a base of some lane */
+    const u8* base = r1 + p_lo;
+    /* plane word w = the 32 bases behind base + 32 w: fetched as they are; what lies behind the window is masked off the planes */
+    auto fetch = [&](int w, u32 (&s)[8]) {
+        if (32 * w < navail) {
+            const u32x4 a = load16_guard(base + 32 * w, seq_end), b = load16_guard(base + 32 * w + 16, seq_end);
+            s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
+            s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+        } else {
+#pragma unroll
+            for (int d = 0; d < 8; d++) s[d] = 0x41414141u; /* (nothing of this lane's: keeps the wave on the short form) */
+        }
+    };
+    const int lane = lane_id();
+    u32* const pl = &park.w[0][0][lane];
+    /* a wave whose 32 x 64 bytes are all exactly A, C, G, T or N -- nearly every one -- takes its planes off three code planes
+       (k_scan's rule); any other byte sends the whole wave through the byte-exact form */
+    auto put = [&](int w, const u32 (&s)[8]) {
+        u32 PA = 0, PC = 0, PT = 0, PG = 0;
+        if (w < nww) { /* wave-uniform */
+            if (!wave_ballot(not_acgtn(s) != 0)) {
+                u32 cL, cH, cN;
+                code_planes<true>(s, cL, cH, cN);
+                letter_planes(cL, cH, cN, PA, PC, PT, PG);
+            } else {
+                build_planes<true>(s, PA, PC, PT, PG);
+            }
+            const int n = navail - 32 * w;
+            const u32 in = n >= 32 ? ~0u : (n <= 0 ? 0u : ((1u << n) - 1u));
+            PA &= in;
+            PC &= in;
+            PT &= in;
+            PG &= in;
+        }
+        u32* const q = pl + (w % RING) * (SLOT / 4);
+        q[0 * 64] = PA;
+        q[1 * 64] = PC;
+        q[2 * 64] = PT;
+        q[3 * 64] = PG;
+        if (w % RING == 0) { /* (wave-uniform) ... and once more behind the last slot of the ring */
+            u32* const q2 = pl + RING * (SLOT / 4);
+            q2[0 * 64] = PA;
+            q2[1 * 64] = PC;
+            q2[2 * 64] = PT;
+            q2[3 * 64] = PG;
+        }
+    };
+#pragma unroll
+    for (int k = 0; k <= RING; k++) pl[k * (SLOT / 4) + 4 * 64] = 0; /* the row the terms behind the adapter point at */
+    u32 s[8];
+#pragma unroll
+    for (int w = 0; w < RING - 1; w++) {
+        fetch(w, s);
+        put(w, s);
+    }
+    fetch(RING - 1, s);
+    const int need = alen - thr; /* matches of a hit */
+    int best = -1;
+    for (int j = 0; j < nwo; j++) { /* wave-uniform trip count */
+        put(j + RING - 1, s);
+        if (j + 1 < nwo) fetch(j + RING, s); /* (in flight while this word is counted) */
+        u32 B[NB];
+        /* terms of bases 0..31: words j, j + 1; of bases 32..63: words j + 1, j + 2 */
+        const int s0 = j % RING, s1 = (j + 1) % RING;
+        match_counts<NB, SLOT, true>(pl + s0 * (SLOT / 4), ad, B, (s1 - s0) * SLOT);
+        const int nv = np - 32 * j; /* this lane's positions from bit 0 of this word on */
+        const u32 vm = nv >= 32 ? ~0u : (nv <= 0 ? 0u : ((1u << nv) - 1u));
+        const u32 hm = need > 0 ? sliced_ge(B, need) & vm : vm;
+        const int p0 = p_lo + 32 * j;
+        int val, pos;
+        if (START) {
+            hit = hm ? p0 + 31 - (int)__clz((int)hm) : hit; /* ascending: the last one stands */
+            sliced_max<NB, false>(B, vm, val, pos);
+            const bool better = vm != 0 && val > best;      /* the first of the minima */
+            cand = better ? p0 + pos : cand;
+            best = better ? val : best;
+        } else {
+            hit = (hm && hit < 0) ? p0 + (int)__ffs((int)hm) - 1 : hit; /* the first one stands */
+            sliced_max<NB, true>(B, vm, val, pos);
+            const bool better = vm != 0 && val >= best;                 /* the last of the minima */
+            cand = better ? p0 + pos : cand;
+            best = better ? val : best;
+        }
+    }
+    if (hit >= 0) cand = -1;
 }
 
 /* passFilter sums over 32 bytes with SWAR byte tricks (quality and base bytes < 128):
@@ -3628,10 +3721,7 @@ __device__ __forceinline__ u32 range_scan_fast(const u8* __restrict__ rb, const 
             if ((npos0 > t0 || npos1 > t0 || packed) && !FPL_DBG(dbg, 16)) { /* wave-uniform: some window of this tile is tested */
                 u32 PA, PC, PT, PG;
                 if (acgt) {
-                    PA = ~(cH | cL); /* (an N has both bits set) */
-                    PC = ~cH & cL;
-                    PT = cH & ~cL;
-                    PG = cH & cL & ~cN;
+                    letter_planes(cL, cH, cN, PA, PC, PT, PG);
                 } else {
                     build_planes(s, PA, PC, PT, PG);
                 }
