@@ -21,14 +21,32 @@ def eof():
     return EOF
 
 
-def bam_header():
+def read_group_lines(header_text):
+    """every line of a BAM header's text (taken to end at its first NUL) that starts with "@RG\\t", verbatim and in order, a
+    line end added where the last one lacks it: what bam_header(read_groups=...) takes"""
+    lines = [l for l in header_text.split(b"\0", 1)[0].splitlines(keepends=True) if l.startswith(b"@RG\t")]
+    if lines and not lines[-1].endswith(b"\n"):
+        lines[-1] += b"\n"
+    return b"".join(lines)
+
+
+def bam_header(read_groups=b""):
     """the BGZF block that opens a BAM file of Engine.set_gzip_records(True) batches: header + the batches' bytes + eof().
-    The 72 bytes are stored, not deflated: every inflater takes that, the device's strict one included."""
-    raw = b"BAM\1" + struct.pack("<i", len(BAM_HEADER_TEXT)) + BAM_HEADER_TEXT + struct.pack("<i", 0)
-    c = zlib.compressobj(0, zlib.DEFLATED, -15)
-    body = c.compress(raw) + c.flush()
-    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", 18 + len(body) + 8 - 1) + body +
-            struct.pack("<II", zlib.crc32(raw) & 0xFFFFFFFF, len(raw)))
+    The bytes are stored, not deflated: every inflater takes that, the device's strict one included.
+    read_groups: with Engine.set_bam_tags(True), the input header's "@RG\\t...\\n" lines (read_group_lines), which go between the
+    @HD and the @PG line so that the records' RG:Z: fields point at something; a header of more than 65 280 bytes takes several
+    blocks, which hold nothing but header."""
+    hd, pg = BAM_HEADER_TEXT.split(b"\n")[0] + b"\n", BAM_HEADER_TEXT.split(b"\n")[1] + b"\n"
+    text = hd + read_groups + pg
+    raw = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", 0)
+    out = []
+    for at in range(0, len(raw), 65280):
+        piece = raw[at:at + 65280]
+        c = zlib.compressobj(0, zlib.DEFLATED, -15)
+        body = c.compress(piece) + c.flush()
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", 18 + len(body) + 8 - 1) + body +
+                   struct.pack("<II", zlib.crc32(piece) & 0xFFFFFFFF, len(piece)))
+    return b"".join(out)
 
 
 class BgzfError(ValueError):

@@ -148,11 +148,17 @@ __device__ __forceinline__ void bamout_wave_quals(u8* __restrict__ dst, const u8
     if (lane < (fl & 15u)) dst[whole + lane] = (u8)bamout::qual_code(src[whole + lane]);
 }
 
+/* what a record gets behind its qualities: nothing (csrc/bam_tags.h has the tail that appends auxiliary fields) */
+struct BamNoTail {
+    __device__ __forceinline__ u8* operator()(u32, int, u32, u32, u8*, u8* d) const { return d; }
+};
 /* a wave per record; comp holds hdr->total bytes (the caller sized it after the layout: comp_cap is checked all the same).
-   blockDim.x is 256: a thread fills one entry of the block's copy of the base table. */
-template <class Src>
+   blockDim.x is 256: a thread fills one entry of the block's copy of the base table.
+   tail(read, fragment, name bytes, bases, the record's first byte, its end so far) -> the record's end */
+template <class Src, class Tail = BamNoTail>
 __device__ __forceinline__ void bamout_compose_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec,
-                                                    const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+                                                    const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap,
+                                                    const Tail& tail = Tail()) {
     __shared__ u8 tab[256];
     tab[threadIdx.x & 255u] = (u8)bamout::base_code(threadIdx.x & 255u);
     __syncthreads();
@@ -187,7 +193,7 @@ __device__ __forceinline__ void bamout_compose_body(const Src& src, const fpl_re
             bamout_wave_pack(pk, g.seq + fs, fl, tab);
             u8* q = pk + ((u64)fl + 1) / 2;
             bamout_wave_quals(q, g.qual + fs, fl);
-            d = q + fl;
+            d = tail(i, f, nl, fl, d, q + fl);
         }
     }
 }

@@ -5,7 +5,8 @@
  *
  * A record is the 36 fixed bytes (block_size, refID -1, pos -1, l_read_name, mapq 0, bin 4680, n_cigar_op 0, flag 4, l_seq,
  * next_refID -1, next_pos -1, tlen 0), the name with its NUL, (l_seq + 1) / 2 bytes of packed bases (high nibble first, the last
- * low nibble 0 when l_seq is odd) and l_seq quality bytes.  No tags.
+ * low nibble 0 when l_seq is odd) and l_seq quality bytes.  No tags -- unless the run keeps the input BAM's (--keep_tags): then the
+ * bytes csrc/bam_tag_rules.h picks follow the qualities and block_size counts them.
  */
 #ifndef FPL_BAM_OUT_RULES_H
 #define FPL_BAM_OUT_RULES_H
@@ -26,7 +27,9 @@ constexpr uint32_t NAME_BYTES = 254; /* bytes of a name: l_read_name is one byte
 constexpr uint32_t BIN = 4680;     /* reg2bin(-1, 0): what every unmapped record carries */
 constexpr uint32_t FLAG = 4;       /* unmapped */
 /* the file's header, uncompressed: magic, l_text, the text, n_ref = 0.  Fixed, so that a file is a function of its reads alone */
-#define FPL_BAMOUT_HEADER_TEXT "@HD\tVN:1.6\tSO:unknown\n@PG\tID:fastplong_amd\tPN:fastplong_amd\n"
+#define FPL_BAMOUT_HEADER_HD "@HD\tVN:1.6\tSO:unknown\n"
+#define FPL_BAMOUT_HEADER_PG "@PG\tID:fastplong_amd\tPN:fastplong_amd\n"
+#define FPL_BAMOUT_HEADER_TEXT FPL_BAMOUT_HEADER_HD FPL_BAMOUT_HEADER_PG /* (--keep_tags: the input's @RG lines between the two) */
 
 /* htslib's seq_nt16_table: '=' -> 0, the letters of "=ACMGRSVTWYHKDBN" in either case -> their code, every other byte -> 15.
    A letter's code is nibble (c & 31) of the two constants (letters outside the alphabet hold 15 there, and so do the five

@@ -27,6 +27,7 @@
 #include "text_parse.h"
 #include "gz_emit.h"
 #include "bam_emit.h"
+#include "bam_tags.h"
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
 #include "bam_walk.h"
@@ -241,6 +242,18 @@ int fpl_assume_inputs_ready(fpl_ctx* ctx, int yes) {
 int fpl_get_batch_forms(const fpl_ctx* ctx, uint64_t out[6]) {
     if (!ctx || !out) return FPL_ERR_ARG;
     for (int i = 0; i < 6; i++) out[i] = ctx->forms[i];
+    return FPL_OK;
+}
+
+int fpl_get_bam_tag_stats(fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    if (!ctx->d_tag_counters.ptr) return FPL_OK; /* (no batch has carried tags yet) */
+    FPL_HIP(hipSetDevice(ctx->device));
+    FPL_HIP(hipStreamSynchronize(ctx->stream)); /* (k_bam_tags of every batch submitted so far has added its share) */
+    unsigned long long c[4];
+    FPL_HIP(hipMemcpy(c, ctx->d_tag_counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; k++) out[k] = c[k];
     return FPL_OK;
 }
 

@@ -144,6 +144,7 @@ __device__ __forceinline__ u32 gz_line_len(const u8* __restrict__ text, u32 at, 
    length arithmetic exist once. */
 /* a TEXT batch: the chunk's text through the line starts and line ends text_parse.h found */
 struct GzTextSrc {
+    typedef GzRec Rec; /* (what rec() gives: a source may hand out more than the pieces -- csrc/bam_tags.h) */
     const u8* text;
     const u32* line;
     const u32* nl_pos;
@@ -165,6 +166,7 @@ struct GzTextSrc {
 /* a BAM batch (bam_decode.h): the name out of the record -- '@' and the l_read_name - 1 bytes at record + 36, so the line is never
    empty --, the bases and qualities out of the decoded arrays (already the twin's: reversed for flag 0x10, min(q, 93) + 33) */
 struct GzBamSrc {
+    typedef GzRec Rec;
     const u8* bam;
     const uint64_t* rec_start;
     const u8* seq;
@@ -227,8 +229,8 @@ __device__ __forceinline__ void gz_cuts(u64 s, u64 e, bool force, F&& emit) {
     if (force || s % GZ_B == 0) emit(s);
     for (u64 m = (s / GZ_B + 1) * GZ_B; m < e; m += GZ_B) emit(m);
 }
-template <class Form = GzFastqForm, class F>
-__device__ __forceinline__ void gz_read_cuts(const GzRec& g, const fpl_read_result& r, u64 o, F&& emit) {
+template <class Form = GzFastqForm, class Rec, class F>
+__device__ __forceinline__ void gz_read_cuts(const Rec& g, const fpl_read_result& r, u64 o, F&& emit) {
     if (r.dropped) return;
     for (int f = 0; f < r.n_frag && f < 2; f++) {
         if (r.code[f] != FPL_PASS_FILTER) continue;
@@ -265,7 +267,7 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
     __syncthreads();
     for (u32 base = 0; base < n_rec; base += 1024) { /* block-uniform */
         const u32 i = base + threadIdx.x;
-        GzRec g = {};
+        typename Src::Rec g = {};
         fpl_read_result r = {};
         u64 len = 0;
         if (i < n_rec) {

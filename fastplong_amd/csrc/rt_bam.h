@@ -64,6 +64,7 @@ int fpl_process_bam_async(fpl_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
     const uint64_t o_begin = off[0], o_end = off[n_reads];
     b.o_begin = o_begin;
     b.bases = o_end - o_begin;
+    b.bytes = n_bytes;
     b.seq_out = seq_out;
     b.qual_out = qual_out;
     FPL_TRY(ensure_host_streams(ctx));
@@ -187,6 +188,7 @@ int fpl_process_bgzf_bam_async(fpl_ctx* ctx, const uint8_t* comp, uint64_t comp_
     FPL_TRY(ensure_bam_tail(ctx));
     const u32 rec_cap = bam_walk_rec_cap(total);
     const uint64_t hi = j.tail_cap + total;
+    b.bytes = hi;
     if (!b.d_whdr.ptr) {
         FPL_HIP(b.d_whdr.alloc(1));
         FPL_HIP(b.h_whdr.alloc(1));

@@ -127,11 +127,14 @@ struct fpl_ctx {
             Event ev;
             bool bgzf = false; /* the context's framing when the batch was submitted (fpl_set_gzip_framing) */
             bool records = false; /* ... and its form: BAM records in place of FASTQ text (fpl_set_gzip_records; BGZF always) */
+            bool tags = false;    /* ... which carry their input records' auxiliary fields (fpl_set_bam_tags; csrc/bam_tags.h) */
+            DevBuf<BamTagInfo> d_tag_info; /* k_bam_tags -> the layout and compose kernels: one per input record */
         } gzip;
         /* a BAM batch: the inflated record bytes, where every record starts, and where the decoded bases go on the host (NULL: a
            gzip batch that leaves them on the device) */
         struct Bam {
             uint64_t o_begin = 0, bases = 0;
+            uint64_t bytes = 0; /* the extent of the record bytes in d_bam: no record, and no aux region, reaches past it */
             uint8_t *seq_out = nullptr, *qual_out = nullptr;
             DevBuf<u8> d_bam;
             DevBuf<uint64_t> d_rec;
@@ -170,6 +173,8 @@ struct fpl_ctx {
     bool bam_gzip = false;     /* fpl_set_bam_gzip */
     bool gzip_bgzf = false;    /* fpl_set_gzip_framing: what the next gzip batch's slot records */
     bool gzip_records = false; /* fpl_set_gzip_records: the same */
+    bool bam_tags = false;     /* fpl_set_bam_tags: the same */
+    DevBuf<unsigned long long> d_tag_counters; /* fpl_get_bam_tag_stats: four counts k_bam_tags adds to (made with the first tagged batch) */
     /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the
        device (csrc/bam_walk.h, csrc/text_walk.h) */
     DevBuf<BamWalkState> d_bamw_state;

@@ -40,7 +40,9 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
         FPL_HIP(g.d_hdr.alloc(1));
         FPL_HIP(g.h_hdr.alloc(1));
     }
-    const uint64_t blk_want = (g.records ? (bam ? bamout_bam_blocks_bound(sl.bam.bases, n) : bamout_blocks_bound(sl.text.bytes, n))
+    const bool tags = g.tags && g.records && bam; /* fpl_set_bam_tags: only where the bytes are BAM records of BAM records */
+    const uint64_t blk_want = (g.records ? (bam ? bamout_bam_blocks_bound(sl.bam.bases, n) + (tags ? bamtag_extra_bound(sl.bam.bytes) / GZ_B + 1 : 0)
+                                                : bamout_blocks_bound(sl.text.bytes, n))
                                          : (bam ? gz_bam_blocks_bound(sl.bam.bases, n) : gz_blocks_bound(sl.text.bytes, n))) + 1;
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
     FPL_HIP(g.d_rec_off.grow((size_t)n + 1, 4096 / sizeof(u64)));
@@ -50,7 +52,20 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
     }
     const u32 blk_cap = (u32)g.d_blk_start.cap;
     hipStream_t st = ctx->stream;
-    if (bam)
+    if (tags) { /* a lane per record walks its aux region, then the layout with the lengths it found */
+        if (!ctx->d_tag_counters.ptr) {
+            FPL_HIP(ctx->d_tag_counters.alloc(4));
+            FPL_HIP(hipMemsetAsync(ctx->d_tag_counters.ptr, 0, 4 * sizeof(unsigned long long), st));
+        }
+        FPL_HIP(g.d_tag_info.grow(n, 4096 / sizeof(BamTagInfo)));
+        hipLaunchKernelGGL(k_bam_tags, dim3(std::max<u32>(1u, std::min<u32>((n + 255) / 256, 8u * ctx->n_cu))), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+                           (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr, (const fpl_read_result*)sl.d_results.ptr, n, (u32)(ctx->hcfg.defer ? 1 : 0),
+                           g.d_tag_info.ptr, ctx->d_tag_counters.ptr);
+        hipLaunchKernelGGL(k_bamout_layout_bam_tags, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, g.d_rec_off.ptr, g.d_blk_start.ptr,
+                           blk_cap - 1, g.d_hdr.ptr);
+    } else if (bam)
         hipLaunchKernelGGL(g.records ? k_bamout_layout_bam : k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
                            (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, g.d_rec_off.ptr, g.d_blk_start.ptr, blk_cap - 1, g.d_hdr.ptr);
@@ -80,7 +95,12 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
     /* (g.records: the bytes are BAM records, csrc/bam_emit.h; the block kernels below do not care) */
-    if (bam_records(sl.kind))
+    if (g.tags && g.records && bam_records(sl.kind))
+        hipLaunchKernelGGL(k_bamout_compose_bam_tags, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+                           (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, (const u64*)g.d_rec_off.ptr,
+                           g.d_comp.ptr, (u64)h.total);
+    else if (bam_records(sl.kind))
         hipLaunchKernelGGL(g.records ? k_bamout_compose_bam : k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
@@ -182,6 +202,7 @@ static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out
     sl.kind = kind;
     sl.gz = gz;
     sl.gzip.records = ctx->gzip_records;
+    sl.gzip.tags = ctx->bam_tags;
     sl.gzip.bgzf = ctx->gzip_bgzf || sl.gzip.records; /* BAM records are BGZF whatever the framing says (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
     sl.n_reads = 0;
     sl.user_results = nullptr;

@@ -124,6 +124,12 @@ int fpl_set_gzip_records(fpl_ctx* ctx, int records) {
     return FPL_OK;
 }
 
+int fpl_set_bam_tags(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    ctx->bam_tags = on != 0; /* (read by slot_begin, like the framing; a slot that holds no BAM records ignores it) */
+    return FPL_OK;
+}
+
 static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
                      const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;

@@ -26,6 +26,7 @@ EXPORTS = [
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing", "fpl_set_gzip_records",
+    "fpl_set_bam_tags", "fpl_get_bam_tag_stats",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
@@ -161,6 +162,11 @@ def load_library(path=None):
     if hasattr(L, "fpl_set_gzip_records"):  # (found by name: without it Engine.set_gzip_records raises)
         L.fpl_set_gzip_records.restype = C.c_int
         L.fpl_set_gzip_records.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "fpl_set_bam_tags"):  # (found by name: without them Engine.set_bam_tags / bam_tag_stats raise)
+        L.fpl_set_bam_tags.restype = C.c_int
+        L.fpl_set_bam_tags.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_get_bam_tag_stats.restype = C.c_int
+        L.fpl_get_bam_tag_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
         L.fpl_inflater_create.restype = C.c_void_p
         L.fpl_inflater_create.argtypes = [C.c_int32]
@@ -734,6 +740,23 @@ class Engine:
         if not hasattr(self.L, "fpl_set_gzip_records"):
             raise FplError("the loaded libfastplong_amd.so has no fpl_set_gzip_records")
         self._check(self.L.fpl_set_gzip_records(self.h, abi.FPL_GZIP_BAM if bam else abi.FPL_GZIP_FASTQ), "fpl_set_gzip_records")
+
+    def set_bam_tags(self, on):
+        """fpl_set_bam_tags: the BAM records of the gzip batches submitted from now on (set_gzip_records(True), submit_bam /
+        submit_bgzf) carry the auxiliary fields of their input records, by the rule of README "BAM output"; the file's header should
+        then repeat the input's @RG lines: fastplong_amd.bgzf.bam_header(read_groups=bgzf.read_group_lines(input header text))"""
+        if not hasattr(self.L, "fpl_set_bam_tags"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_bam_tags")
+        self._check(self.L.fpl_set_bam_tags(self.h, 1 if on else 0), "fpl_set_bam_tags")
+
+    def bam_tag_stats(self):
+        """fpl_get_bam_tag_stats -> (records that kept every field, records that lost positional fields, tag bytes written, records
+        whose region did not parse to its end), per output record since the engine was made"""
+        if not hasattr(self.L, "fpl_get_bam_tag_stats"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_tag_stats")
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.fpl_get_bam_tag_stats(self.h, out), "fpl_get_bam_tag_stats")
+        return tuple(int(v) for v in out)
 
     def gzip_batches(self):
         """batches whose gzip member was made on the device (fpl_get_gzip_batches)"""

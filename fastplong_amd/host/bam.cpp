@@ -12,6 +12,7 @@
 #include "gzip.h"
 #include "pool.h"
 #include "../csrc/bam_rules.h"
+#include "../csrc/bam_tag_rules.h"
 
 using namespace std;
 
@@ -227,6 +228,7 @@ bool BamReader::walk(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint64_t 
             p += 4;
         }
         header_done_ = true;
+        header_text_.assign((const char*)base + 8, (size_t)rd32(base + 4));
         wpos_ = p;
     }
     for (;;) {
@@ -272,6 +274,11 @@ bool BamReader::walk(Batch& b, uint64_t max_bytes, uint32_t max_reads, uint64_t 
         }
         if (rule::paired(flag)) return fail("flag 0x1 (paired-end) -- fastplong is single-end", true);
         if (rule::no_qualities(f, l_seq ? qual[0] : 0)) return fail("no qualities (the first quality byte is 0xFF)", true);
+        if (check_tags_) {
+            uint64_t at, len;
+            fpl::bamtag::region(r, at, len);
+            if (!fpl::bamtag::walk(r + at, len, fpl::bamtag::ByteScan()).whole) return fail("the auxiliary fields do not parse", true);
+        }
         const size_t nl = strnlen((const char*)name, l_name - 1);
         const size_t t = b.text.size();
         b.text.resize(t + 1 + nl + 1);
@@ -410,7 +417,7 @@ namespace {
 struct BamAll {
     vector<uint8_t> bytes;
     vector<uint64_t> rec, off{0};
-    string names, err, warn;
+    string names, err, warn, header;
     uint32_t batches = 0;
     uint64_t on_device = 0, refused = 0;
 };
@@ -425,11 +432,12 @@ void* fplh_bam_read_all(const char* path, uint64_t chunk_bytes, uint32_t max_rea
 uint64_t fplh_bam_all_device(void* h) { return ((BamAll*)h)->on_device; }
 uint64_t fplh_bam_all_refused(void* h) { return ((BamAll*)h)->refused; }
 
-void* fplh_bam_read_all_with(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes, fplh::BgzfInflateFn fn,
-                             void* user) {
+static void* bam_read_all(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes, fplh::BgzfInflateFn fn,
+                          void* user, bool check_tags) {
     fplh::BamReader rd(path);
     if (!rd.ok()) return nullptr;
     rd.set_inflater(fn, user);
+    rd.set_check_tags(check_tags);
     if (window_bytes) rd.set_window_bytes(window_bytes);
     BamAll* a = new BamAll;
     for (;;) {
@@ -448,9 +456,21 @@ void* fplh_bam_read_all_with(const char* path, uint64_t chunk_bytes, uint32_t ma
     }
     a->err = rd.error();
     a->warn = rd.warning();
+    a->header = rd.header_text();
     a->on_device = rd.blocks_on_device();
     a->refused = rd.blocks_refused();
     return a;
+}
+void* fplh_bam_read_all_with(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes, fplh::BgzfInflateFn fn,
+                             void* user) {
+    return bam_read_all(path, chunk_bytes, max_reads, window_bytes, fn, user, false);
+}
+void* fplh_bam_read_all_tags(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes) {
+    return bam_read_all(path, chunk_bytes, max_reads, window_bytes, nullptr, nullptr, true);
+}
+const char* fplh_bam_all_header(void* h, uint64_t* n) {
+    *n = ((BamAll*)h)->header.size();
+    return ((BamAll*)h)->header.data();
 }
 uint32_t fplh_bam_all_n(void* h) { return (uint32_t)((BamAll*)h)->rec.size(); }
 uint32_t fplh_bam_all_batches(void* h) { return ((BamAll*)h)->batches; }

@@ -67,6 +67,11 @@ class BamReader {
     }
     uint64_t blocks_on_device() const { return dev_blocks_; }     /* blocks the inflater vouched for */
     uint64_t blocks_refused() const { return refused_blocks_; }   /* blocks it was given and the host inflated again */
+    /* --keep_tags: the walk also walks the auxiliary fields of every record it does not skip (csrc/bam_tag_rules.h); a record
+       whose fields do not parse to the end of the record ends the input like every other damaged record */
+    void set_check_tags(bool on) { check_tags_ = on; }
+    /* the header's text (l_text bytes), known once the first fill has walked the header; "" before */
+    const std::string& header_text() const { return header_text_; }
     /* test hook: inflated bytes per window (default 8 MiB; at least one block is always taken) */
     void set_window_bytes(uint64_t w) { window_ = w ? w : 1; }
 
@@ -93,6 +98,8 @@ class BamReader {
     uint64_t wpos_ = 0;      /* walk position in the current batch's b.bam */
     uint64_t need_ = 0;      /* bytes from wpos_ the walk needs before it can go on */
     bool header_done_ = false;
+    bool check_tags_ = false;
+    std::string header_text_;
     bool last_was_eof_block_ = false;
     bool done_ = false;
     uint64_t rec_no_ = 0;
@@ -123,6 +130,9 @@ const uint64_t* fplh_bam_all_off(void* h);  /* n + 1 output offsets */
 const char* fplh_bam_all_names(void* h, uint64_t* n); /* the name lines ("@name"), each followed by '\n' */
 const char* fplh_bam_all_error(void* h);
 const char* fplh_bam_all_warning(void* h);
+/* the same reader with set_check_tags(true); fplh_bam_all_header: the header's text as the reader took it */
+void* fplh_bam_read_all_tags(const char* path, uint64_t chunk_bytes, uint32_t max_reads, uint64_t window_bytes);
+const char* fplh_bam_all_header(void* h, uint64_t* n);
 void fplh_bam_all_free(void* h);
 }
 #endif

@@ -7,25 +7,84 @@
 #include <algorithm>
 
 #include "../csrc/bam_out_rules.h"
+#include "../csrc/bam_tag_rules.h"
 
 namespace fplh {
 
 namespace rule = fpl::bamout;
+namespace tagrule = fpl::bamtag;
+
+namespace {
+/* magic, l_text, the text, n_ref = 0 */
+std::string header_of(const std::string& text) {
+    std::string s("BAM\1", 4);
+    const uint32_t l_text = (uint32_t)text.size();
+    for (int k = 0; k < 4; k++) s += (char)(l_text >> (8 * k));
+    s += text;
+    s.append(4, '\0'); /* n_ref */
+    return s;
+}
+/* the Z / H scan of the shared walk, by memchr */
+struct MemScan {
+    uint64_t operator()(const uint8_t* v, uint64_t left) const {
+        const void* z = left ? memchr(v, 0, (size_t)left) : nullptr;
+        return z ? (uint64_t)((const uint8_t*)z - v) + 1 : 0;
+    }
+};
+/* what the rule picks of the input record at rec, appended to out -> the bytes appended */
+uint64_t append_tags(const uint8_t* rec, bool changed, std::string& out, uint64_t* stats) {
+    uint64_t at, len;
+    tagrule::region(rec, at, len);
+    const uint8_t* p = rec + at;
+    const tagrule::Walk w = tagrule::walk(p, len, MemScan());
+    uint64_t wrote = w.prefix;
+    if (!changed || !w.positional) {
+        out.append((const char*)p, (size_t)w.prefix);
+    } else { /* the non-positional fields, in their order */
+        wrote = w.kept;
+        for (uint64_t o = 0; o < w.prefix;) {
+            const uint64_t n = tagrule::field_len(p + o, w.prefix - o, MemScan());
+            if (!tagrule::positional(p + o)) out.append((const char*)p + o, (size_t)n);
+            o += n;
+        }
+    }
+    if (stats) {
+        stats[changed && w.positional ? 1 : 0]++;
+        stats[2] += wrote;
+        if (!w.whole) stats[3]++;
+    }
+    return wrote;
+}
+}  // namespace
 
 const std::string& bam_header_bytes() {
-    static const std::string h = [] {
-        const std::string text = FPL_BAMOUT_HEADER_TEXT;
-        std::string s("BAM\1", 4);
-        const uint32_t l_text = (uint32_t)text.size();
-        for (int k = 0; k < 4; k++) s += (char)(l_text >> (8 * k));
-        s += text;
-        s.append(4, '\0'); /* n_ref */
-        return s;
-    }();
+    static const std::string h = header_of(FPL_BAMOUT_HEADER_TEXT);
     return h;
 }
+std::string bam_header_bytes(const std::string& read_groups) {
+    return header_of(std::string(FPL_BAMOUT_HEADER_HD) + read_groups + FPL_BAMOUT_HEADER_PG);
+}
+std::string bam_read_group_lines(const std::string& header_text) {
+    const size_t end = std::min(header_text.size(), header_text.find('\0'));
+    std::string out;
+    for (size_t at = 0; at < end;) {
+        const size_t nl = header_text.find('\n', at);
+        const size_t e = nl == std::string::npos || nl >= end ? end : nl + 1;
+        if (e - at >= 4 && header_text.compare(at, 4, "@RG\t") == 0) out.append(header_text, at, e - at);
+        at = e;
+    }
+    if (!out.empty() && out.back() != '\n') out += '\n';
+    return out;
+}
 
-void fastq_to_bam_records(const std::string& text, std::string& out) {
+size_t fastq_record_count(const std::string& text) {
+    return (size_t)std::count(text.begin(), text.end(), '\n') / 4;
+}
+
+void fastq_to_bam_records(const std::string& text, std::string& out) { fastq_to_bam_records(text, nullptr, 0, out, nullptr); }
+
+void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats) {
+    size_t k = 0; /* the record's place in the text */
     static const struct Table {
         uint8_t t[256];
         Table() { rule::base_table(t); }
@@ -68,6 +127,11 @@ void fastq_to_bam_records(const std::string& text, std::string& out) {
         const uint32_t n_q = (uint32_t)std::min<size_t>((size_t)(qual_e - qual), l_seq);
         for (uint32_t i = 0; i < n_q; i++) d[i] = (uint8_t)rule::qual_code(qual[i]);
         for (uint32_t i = n_q; i < l_seq; i++) d[i] = 0;
+        if (k < n_src && src[k].rec) { /* (d is no use behind this: out grows) */
+            const uint64_t bs = rule::record_len(nl, l_seq) - 4u + append_tags(src[k].rec, src[k].changed, out, stats);
+            for (int b = 0; b < 4; b++) out[at + (size_t)b] = (char)(bs >> (8 * b));
+        }
+        k++;
         p = qual_e < end ? qual_e + 1 : end;
     }
 }

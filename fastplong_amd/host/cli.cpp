@@ -63,7 +63,7 @@ int main(int argc, char* argv[]) {
         fplh::ByteBuf::set_allocator(fpl_host_alloc, fpl_host_free);
 
     InputPlan plan = plan_input(opt, facts, api);
-    Outputs outs = open_outputs(opt);
+    Outputs outs = open_outputs(opt, facts.bamReadGroups);
     Pipeline pipeline(opt, api, facts, plan, outs, ctxs);
     pipeline.run();
     if (opt.verbose) print_pipeline_summary(pipeline);

@@ -38,6 +38,11 @@ struct DeviceApi {
     SetGzipFn set_gzip_framing = nullptr;
     /* --out *.bam: the device's gzip batches are BAM records in BGZF blocks (found by name; without it the host converts and frames) */
     SetGzipFn set_gzip_records = nullptr;
+    /* --keep_tags: ... and those records carry the input records' auxiliary fields (found by name; without it the host writes
+       every record of such a run) */
+    typedef int (*BamTagStatsFn)(fpl_ctx*, uint64_t*);
+    SetGzipFn set_bam_tags = nullptr;
+    BamTagStatsFn get_bam_tag_stats = nullptr;
 };
 
 static DeviceApi load_device_api() {
@@ -54,6 +59,8 @@ static DeviceApi load_device_api() {
     a.wait_bam_gz = (DeviceApi::WaitBamGzFn)dlsym(RTLD_DEFAULT, "fpl_wait_bam_gz");
     a.set_gzip_framing = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_framing");
     a.set_gzip_records = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_records");
+    a.set_bam_tags = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_tags");
+    a.get_bam_tag_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_tag_stats");
     return a;
 }
 

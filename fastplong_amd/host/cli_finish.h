@@ -34,6 +34,17 @@ static void print_pipeline_summary(const Pipeline& p) {
         cerr << "device gzip: " << p.nDevGz.load() << " members deflated on the device (in the waits above)" << endl;
     if (p.out.fout && p.out.fout.bam) cerr << "BAM records: BGZF blocks framed on the device: " << p.nDevBgzf.load() << " (every other block by the host)" << endl;
     else if (p.opt.bgzf) cerr << "BGZF blocks framed on the device: " << p.nDevBgzf.load() << " (every other block by the host)" << endl;
+    if (p.opt.keepTags) { /* both forms: the host's converter and, where the library has the call, every context's kernels */
+        uint64_t t[4];
+        for (int k = 0; k < 4; k++) t[k] = g_bamTagStats[k].load();
+        for (fpl_ctx* ctx : p.ctxs) {
+            uint64_t c[4] = {0, 0, 0, 0};
+            if (p.api.get_bam_tag_stats && p.api.get_bam_tag_stats(ctx, c) == FPL_OK)
+                for (int k = 0; k < 4; k++) t[k] += c[k];
+        }
+        cerr << "BAM tags: " << t[0] << " records kept every field, " << t[1] << " lost positional fields (MM, ML, MN, B arrays), " << t[2]
+             << " bytes" << endl;
+    }
     if (in.textMode)
         cerr << "device parse: " << p.nTextBatches.load() << " chunks parsed on the device, " << p.nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;

@@ -7,6 +7,7 @@
 #define FPLH_CLI_INPUT_H
 
 #include "cli_device.h"
+#include "bam_out.h"
 #include "evaluator.h"
 #include "fastq.h"
 #include "gzip.h"
@@ -15,6 +16,7 @@
 struct InputFacts {
     bool bam = false;         /* BAM input (host/bam.h): recognised by its content; its bases are decoded on the device */
     bool isRNA = false;
+    string bamReadGroups;     /* --keep_tags: the @RG lines of the input's header, as the outputs' headers repeat them */
     void* inflater = nullptr; /* --device_inflate: the first device's inflater (fpl_inflater_create) for BGZF blocks or a one-member .gz, or none */
 };
 
@@ -24,6 +26,7 @@ struct InputFacts {
 static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
     InputFacts in;
     in.bam = !opt.from_stdin && fplh::is_bam_file(opt.in);
+    if (opt.keepTags && !in.bam) error_exit("--keep_tags needs BAM input (--in " + opt.in + " is not a BAM file)");
     if (in.bam) {
         const DeviceApi::BamDecodeFn bamDecode = api.decode_bam;
         if (!api.process_bam_async || !bamDecode)
@@ -54,6 +57,7 @@ static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
         fplh::Batch b;
         if (in.bam) {
             fplh::read_bam_prefix(opt.in, b, 100, 1L << 62);
+            if (opt.keepTags) in.bamReadGroups = fplh::bam_read_group_lines(fplh::bam_prefix_header_text());
         } else {
             fplh::FastqReader ev(opt.in);
             if (!ev.ok()) error_exit("Failed to open file: " + opt.in);
@@ -231,6 +235,7 @@ static InputPlan plan_input(const Options& opt, const InputFacts& in, const Devi
         p.bamReader = new fplh::BamReader(opt.in);
         if (!p.bamReader->ok()) error_exit("Failed to open file: " + opt.in);
         if (in.inflater) p.bamReader->set_inflater(api.inflate_bgzf, in.inflater);
+        p.bamReader->set_check_tags(opt.keepTags);
     } else if (!p.chunked) {
         p.reader = new fplh::FastqReader(opt.in);
         if (!p.reader->ok()) error_exit("Failed to open file: " + opt.in);

@@ -6,6 +6,7 @@
 #define FPLH_CLI_OUTPUT_H
 
 #include "bam_out.h"
+#include "bam_tags.h"
 #include "cli_options.h"
 #include "gzip.h"
 #include "pool.h"
@@ -43,10 +44,11 @@ struct OutFile {
         return o;
     }
     /* *.bam: the header's block, before the first piece (a file no read reaches is this block and the EOF block) */
-    void write_bam_header(int gzLevel) {
+    /* readGroups: --keep_tags, the input's @RG lines (a header past 65 280 bytes takes several blocks, which hold nothing else) */
+    void write_bam_header(int gzLevel, const string* readGroups = nullptr) {
         if (!f || !bam) return;
         string h;
-        fplh::bgzf_into(fplh::bam_header_bytes(), gzLevel, h);
+        fplh::bgzf_into(readGroups ? fplh::bam_header_bytes(*readGroups) : fplh::bam_header_bytes(), gzLevel, h);
         if (positional ? pwrite(fileno(f), h.data(), h.size(), 0) != (ssize_t)h.size() : fwrite(h.data(), 1, h.size(), f) != h.size())
             error_exit("write failed");
         pos = h.size();
@@ -102,8 +104,12 @@ struct OutFile {
     }
 };
 
+/* --keep_tags: what the host's converter counted (bam_out.h), over every formatter thread */
+static std::atomic<uint64_t> g_bamTagStats[4];
+
 struct Outputs {
     OutFile fout, ffail;
+    bool keepTags = false; /* --keep_tags: a .bam output's records carry their input record's auxiliary fields */
     int gzLevel = 4;
     bool bgzf = false; /* --bgzf: the pieces are framed by bgzf_into */
     fplh::SplitOutput* split = nullptr; /* --split / --split_by_lines: the workers' private writers take the passing reads */
@@ -111,12 +117,18 @@ struct Outputs {
 
     bool any_gz() const { return (fout && fout.gz) || (ffail && ffail.gz); }
     /* the pieces as `file` takes them (in parallel; pieces stay below 4 GiB: one slice of a batch) */
-    void gzip_pieces(vector<string>& pieces, const OutFile& file) const {
+    /* tags: --keep_tags, the sources of the records of ALL pieces together, in their order (bam_tags.h) */
+    void gzip_pieces(vector<string>& pieces, const OutFile& file, const vector<fplh::BamTagSrc>* tags = nullptr) const {
         const int level = gzLevel;
         const bool blocks = file.bgzf, records = file.bam;
+        if (records && tags) {
+            uint64_t st[4] = {0, 0, 0, 0};
+            fplh::pieces_to_bam_records(pieces, *tags, st);
+            for (int k = 0; k < 4; k++) g_bamTagStats[k] += st[k];
+        }
         fplh::parallel_run((int)pieces.size(), [&](int i) {
             if (pieces[i].empty()) return;
-            if (records) {
+            if (records && !tags) {
                 string rec;
                 fplh::fastq_to_bam_records(pieces[i], rec);
                 pieces[i].swap(rec);
@@ -131,7 +143,7 @@ struct Outputs {
     }
 };
 
-static Outputs open_outputs(const Options& opt) {
+static Outputs open_outputs(const Options& opt, const string& bamReadGroups = string()) {
     Outputs o;
     /* with --split* the reference never calls initOutput (src/seprocessor.cpp:65-67): no single --out file and no
        --failed_out either; the workers' private writers take the passing reads */
@@ -140,8 +152,9 @@ static Outputs open_outputs(const Options& opt) {
     o.ffail = OutFile::open(opt.splitEnabled ? string() : opt.failedOut, opt.bgzf);
     if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.bgzf = false, o.fout.bam = false, o.fout.positional = false;
     o.gzLevel = min(9, max(1, opt.compression));
-    o.fout.write_bam_header(o.gzLevel);
-    o.ffail.write_bam_header(o.gzLevel);
+    o.keepTags = opt.keepTags;
+    o.fout.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
+    o.ffail.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     if (opt.splitEnabled)
         o.split = new fplh::SplitOutput(opt.out, opt.splitDigits, opt.workers, opt.splitByLines, opt.splitNumber, opt.splitSize, o.gzLevel, opt.bgzf);
     /* Plain --out alone that is NOT a regular file -- a pipe into an aligner or a compressor (--stdout, /dev/stdout), /dev/null --

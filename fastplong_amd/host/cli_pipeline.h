@@ -25,6 +25,7 @@ struct Work {
     vector<fpl_read_result> res;
     fplh::FragmentList frags; /* --break / --mask */
     vector<string> outs, faileds;
+    vector<fplh::BamTagSrc> outTags, failedTags; /* --keep_tags: where the records of outs / faileds take their auxiliary fields from */
     string gz_member;  /* --out *.gz deflated on the device (fpl_wait_text_gz): this batch's gzip member, written as it is */
     bool dev_gz = false;
     bool dev_gz_empty = false; /* a gzip BAM batch in which nothing passed: --out gets nothing, and the decoded arrays may never have come back */
@@ -289,7 +290,13 @@ void Pipeline::enable_device_gzip() {
        alike (README "BAM output": not the default until whole-run numbers exist); a library without fpl_set_gzip_records leaves
        everything to the host, without a word.  Records are BGZF by themselves: --bgzf changes nothing for them. */
     const bool bamOut = out.fout && out.fout.bam;
+    /* --keep_tags: the device form needs fpl_set_bam_tags besides; against a library without it the host writes every record */
+    if (bamOut && opt.keepTags) eligible = eligible && api.set_bam_tags != nullptr;
     if (bamOut) eligible = eligible && opt.deviceGzip && (in.textMode || facts.bam) && (devBamOut = frame_on_all(api.set_gzip_records, ctxs));
+    if (bamOut && opt.keepTags && devBamOut && !enable_on_all(api.set_bam_tags, true, ctxs)) { /* (a context refused: the host's form) */
+        for (fpl_ctx* c : ctxs) (void)api.set_gzip_records(c, FPL_GZIP_FASTQ);
+        eligible = devBamOut = false;
+    }
     if (eligible && !bamOut && opt.bgzf && (in.textMode || (facts.bam && opt.deviceGzip))) eligible = devBgzf = frame_on_all(api.set_gzip_framing, ctxs);
     if (eligible && in.textMode) devGz = enable_on_all(api.set_text_gzip, api.wait_text_gz != nullptr, ctxs);
     /* the same for BAM input (fpl_set_bam_gzip / fpl_wait_bam_gz, C-ABI version 10): the device composes the member from the
@@ -693,11 +700,16 @@ void Pipeline::format_stage(int f) {
         } else if (w->rc == FPL_OK && !out.split) { /* (--split* output is cut per pack of 16 reads by the writer) */
             fplh::format_batch_parallel(w->batch, w->res.data(), fmtThreads, w->outs, toFailed ? &w->faileds : nullptr,
                                         opt.fragmentMode ? &w->frags : nullptr);
+            /* --keep_tags: which input record every record of the pieces came from, by the formatter's own order */
+            const fplh::FragmentList* fl = opt.fragmentMode ? &w->frags : nullptr;
+            const bool tagOut = out.keepTags && out.fout && out.fout.bam && !w->dev_gz, tagFailed = out.keepTags && toFailed && out.ffail.bam;
+            if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags);
+            if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags);
             if (w->dev_gz) { /* (formatted for --failed_out alone) */
                 w->outs.resize(1);
                 w->outs[0].swap(w->gz_member);
-            } else if (out.fout && out.fout.gz) out.gzip_pieces(w->outs, out.fout);
-            if (toFailed && out.ffail.gz) out.gzip_pieces(w->faileds, out.ffail);
+            } else if (out.fout && out.fout.gz) out.gzip_pieces(w->outs, out.fout, tagOut ? &w->outTags : nullptr);
+            if (toFailed && out.ffail.gz) out.gzip_pieces(w->faileds, out.ffail, tagFailed ? &w->failedTags : nullptr);
         }
         tFormat[(size_t)f] += now_s() - t1;
         doneq.push(w);

@@ -181,6 +181,8 @@ void set_bam_decoder(BamDecoder f) { g_bam_decoder = std::move(f); }
 static BgzfInflateFn g_bam_inflate = nullptr;
 static void* g_bam_inflate_user = nullptr;
 static uint64_t g_prefix_on_device = 0, g_prefix_refused = 0;
+static string g_prefix_header_text;
+const string& bam_prefix_header_text() { return g_prefix_header_text; }
 void set_bam_inflater(BgzfInflateFn fn, void* user) {
     g_bam_inflate = fn;
     g_bam_inflate_user = user;
@@ -197,6 +199,7 @@ long read_bam_prefix(const string& path, Batch& b, long read_limit, long base_li
     struct Count { /* whichever way this function is left */
         BamReader& r;
         ~Count() {
+            g_prefix_header_text = r.header_text();
             g_prefix_on_device += r.blocks_on_device();
             g_prefix_refused += r.blocks_refused();
         }

@@ -49,6 +49,9 @@ void set_bam_decoder(BamDecoder f);
  * and its handle); the counts are the blocks the prefix readers had inflated that way / had to inflate again */
 void set_bam_inflater(int (*fn)(void*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t, uint8_t*, uint64_t), void* user);
 void bam_prefix_block_counts(uint64_t& on_device, uint64_t& refused);
+/* the header text of the BAM the last read_bam_prefix read ("" when it did not get that far): --keep_tags takes the @RG lines of
+   the output's header from it, before the outputs open */
+const std::string& bam_prefix_header_text();
 class BamReader;
 struct Batch;
 /* up to read_limit records / base_limit bases of a BAM input, decoded (b: a CSR batch afterwards); the read-count estimate

@@ -9,8 +9,11 @@
 #include <condition_variable>
 #include <mutex>
 
+#include "bam.h"
 #include "bam_out.h"
+#include "bam_tags.h"
 #include "../csrc/bam_out_rules.h"
+#include "../csrc/bam_tag_rules.h"
 #include "fastq.h"
 #include "gzip.h"
 #include "pool.h"
@@ -238,6 +241,56 @@ int fplh_bam_header_bytes(char** out, uint64_t* out_len) {
     *out = (char*)malloc(h.size());
     if (*out) memcpy(*out, h.data(), h.size());
     return *out ? 0 : -1;
+}
+/* test hooks of --keep_tags.  _header_rg: the file header with the @RG lines of an input header's text (mode 0) or with `text`
+   itself as the lines (mode 1); _walk: the shared rule's walk of a region (prefix, kept, positional, whole); _region: where the
+   region of the record at rec lies */
+int fplh_bam_header_rg(const char* text, uint64_t n, int mode, char** out, uint64_t* out_len) {
+    const std::string t(text ? text : "", (size_t)n);
+    hand_out(fplh::bam_header_bytes(mode ? t : fplh::bam_read_group_lines(t)), out, out_len);
+    return 0;
+}
+void fplh_bam_tag_walk(const uint8_t* p, uint64_t len, uint64_t* out) {
+    const fpl::bamtag::Walk w = fpl::bamtag::walk(p, len, fpl::bamtag::ByteScan());
+    out[0] = w.prefix, out[1] = w.kept, out[2] = w.positional, out[3] = w.whole;
+}
+void fplh_bam_tag_region(const uint8_t* rec, uint64_t* at, uint64_t* len) { fpl::bamtag::region(rec, *at, *len); }
+/* the host form as the CLI runs it: the BAM file at `path` read into ONE batch (BamReader), its decoded bases and qualities and
+   its results (and, with n_frags != ~0u, the fragment list of a --break / --mask run) given by the caller; formatted in `threads`
+   pieces, the sources derived (bam_tag_sources), the pieces converted (pieces_to_bam_records).  out / failed: the uncompressed
+   records of --out / --failed_out; stats: four counts each.  -1: the file did not read to its end as one batch of n reads */
+int fplh_bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n,
+                      const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
+                      uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats) {
+    fplh::BamReader rd(path);
+    if (!rd.ok()) return -1;
+    Batch b;
+    if (rd.fill(b, ~0ull, 0x3FFFFFFFu) != n || !rd.error().empty() || b.n() != n) return -1;
+    if (b.seq.size()) {
+        memcpy(b.seq.data(), seq, b.seq.size());
+        memcpy(b.qual.data(), qual, b.seq.size());
+    }
+    fplh::FragmentList fl;
+    const bool fragments = n_frags != ~0u;
+    if (fragments) {
+        fl.frags.assign(frags, frags + n_frags);
+        fl.regs.assign(regs, regs + n_regs);
+        fl.index(n);
+    }
+    std::vector<std::string> o, f;
+    fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
+    std::vector<fplh::BamTagSrc> so, sf;
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so);
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf);
+    for (int k = 0; k < 8; k++) stats[k] = 0;
+    fplh::pieces_to_bam_records(o, so, stats);
+    fplh::pieces_to_bam_records(f, sf, stats + 4);
+    std::string oo, ff;
+    for (auto& x : o) oo += x;
+    for (auto& x : f) ff += x;
+    hand_out(oo, out, out_len);
+    hand_out(ff, failed, failed_len);
+    return 0;
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */

@@ -479,6 +479,31 @@ enum { FPL_GZIP_FASTQ = 0, FPL_GZIP_BAM = 1 };
 int fpl_set_gzip_records(fpl_ctx* ctx, int records);
 
 /*
+ * The auxiliary fields of a BAM input's records in the BAM records of a gzip batch (README "BAM output", --keep_tags).
+ * FPL_ABI_VERSION stays 10: both calls are found by symbol lookup; a caller of a library without them writes such records on the host.
+ *
+ *   fpl_set_bam_tags   per context; on != 0 takes effect with the NEXT submission, like fpl_set_gzip_records.  It changes the
+ *                      bytes of a gzip batch only where the batch holds BAM records (fpl_process_bam_async,
+ *                      fpl_process_bgzf_bam_async) AND its bytes are BAM records (FPL_GZIP_BAM); every other batch ignores it.
+ *                      Then an output record carries, right behind its qualities and counted by its block_size, fields of the input
+ *                      record its read came from.  The input record's aux region is what lies between its qualities and its end
+ *                      (4 + block_size, never past the bytes submitted).  Fields are taken from its front -- two tag bytes, a
+ *                      type, a value: A c C 1 byte, s S 2, i I f 4, Z H up to and including the first NUL, B a subtype of
+ *                      cCsSiIf, a u32 count and count values -- up to the first that does not parse: the parsed prefix.  An output
+ *                      record that is the only fragment of its read (n_frag 1, kind 0), all of it, of an input record without flag
+ *                      0x10, in a context without --break / --mask gets the prefix verbatim; every other one gets the prefix
+ *                      without its positional fields (type B, or tag MM Mm ML Ml MN), in their order.  Both fragments of a split
+ *                      read carry the read's fields.  Nothing else of the records changes; the deflate blocks are cut by the
+ *                      same rule, and a batch is at most twice its input record bytes longer than without the switch.
+ *                      The file's header is the caller's: it should repeat the input's @RG lines (the CLI does).
+ *   fpl_get_bam_tag_stats   out[4], counted per output record since the context was made: records that kept every field of
+ *                      their parsed prefix, records that lost positional fields, tag bytes written, records whose region did not
+ *                      parse to its end.  It waits for the kernels of every batch submitted so far.
+ */
+int fpl_set_bam_tags(fpl_ctx* ctx, int on);
+int fpl_get_bam_tag_stats(fpl_ctx* ctx, uint64_t* out);
+
+/*
  * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
  * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
  * caller then inflates on the host.
