@@ -129,6 +129,10 @@ struct fpl_ctx {
             bool records = false; /* ... and its form: BAM records in place of FASTQ text (fpl_set_gzip_records; BGZF always) */
             bool tags = false;    /* ... which carry their input records' auxiliary fields (fpl_set_bam_tags; csrc/bam_tags.h) */
             DevBuf<BamTagInfo> d_tag_info; /* k_bam_tags -> the layout and compose kernels: one per input record */
+            bool mods = false;    /* ... with MM / ML / MN re-indexed (fpl_set_bam_mods; csrc/bam_mods.h) */
+            DevBuf<BamModInfo> d_mod_info; /* k_bam_tags_mods -> k_bam_mods_plan and the compose kernel: one per input record */
+            DevBuf<u32> d_mod_cand;        /* the candidate records */
+            DevBuf<BamModPlan> d_mod_plan; /* one per candidate (sized for every record: how many there are only the device knows) */
         } gzip;
         /* a BAM batch: the inflated record bytes, where every record starts, and where the decoded bases go on the host (NULL: a
            gzip batch that leaves them on the device) */
@@ -174,6 +178,8 @@ struct fpl_ctx {
     bool gzip_bgzf = false;    /* fpl_set_gzip_framing: what the next gzip batch's slot records */
     bool gzip_records = false; /* fpl_set_gzip_records: the same */
     bool bam_tags = false;     /* fpl_set_bam_tags: the same */
+    bool bam_mods = false;     /* fpl_set_bam_mods: the same */
+    DevBuf<unsigned long long> d_mod_counters; /* fpl_get_bam_mod_stats: four counts, and the candidates of the batch in flight (csrc/bam_mods.h) */
     DevBuf<unsigned long long> d_tag_counters; /* fpl_get_bam_tag_stats: four counts k_bam_tags adds to (made with the first tagged batch) */
     /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the
        device (csrc/bam_walk.h, csrc/text_walk.h) */

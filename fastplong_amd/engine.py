@@ -26,7 +26,7 @@ EXPORTS = [
     "fpl_process_text_async", "fpl_wait_text", "fpl_peek_text", "fpl_start_text", "fpl_cancel_text",
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing", "fpl_set_gzip_records",
-    "fpl_set_bam_tags", "fpl_get_bam_tag_stats",
+    "fpl_set_bam_tags", "fpl_get_bam_tag_stats", "fpl_set_bam_mods", "fpl_get_bam_mod_stats",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
@@ -167,6 +167,11 @@ def load_library(path=None):
         L.fpl_set_bam_tags.argtypes = [C.c_void_p, C.c_int]
         L.fpl_get_bam_tag_stats.restype = C.c_int
         L.fpl_get_bam_tag_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "fpl_set_bam_mods"):  # (the same for Engine.set_bam_mods / bam_mod_stats)
+        L.fpl_set_bam_mods.restype = C.c_int
+        L.fpl_set_bam_mods.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_get_bam_mod_stats.restype = C.c_int
+        L.fpl_get_bam_mod_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
         L.fpl_inflater_create.restype = C.c_void_p
         L.fpl_inflater_create.argtypes = [C.c_int32]
@@ -756,6 +761,22 @@ class Engine:
             raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_tag_stats")
         out = (C.c_uint64 * 4)()
         self._check(self.L.fpl_get_bam_tag_stats(self.h, out), "fpl_get_bam_tag_stats")
+        return tuple(int(v) for v in out)
+
+    def set_bam_mods(self, on):
+        """fpl_set_bam_mods: with set_bam_tags(True), the trimmed and split records of the batches submitted from now on get their
+        MM / ML / MN fields re-indexed for their piece of the read (README "BAM output", --keep_mods) in place of losing them"""
+        if not hasattr(self.L, "fpl_set_bam_mods"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_bam_mods")
+        self._check(self.L.fpl_set_bam_mods(self.h, 1 if on else 0), "fpl_set_bam_mods")
+
+    def bam_mod_stats(self):
+        """fpl_get_bam_mod_stats -> (output records re-indexed, changed records whose modification fields were not re-indexable
+        and were dropped, modification positions kept, positions cut away), since the engine was made"""
+        if not hasattr(self.L, "fpl_get_bam_mod_stats"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_mod_stats")
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.fpl_get_bam_mod_stats(self.h, out), "fpl_get_bam_mod_stats")
         return tuple(int(v) for v in out)
 
     def gzip_batches(self):

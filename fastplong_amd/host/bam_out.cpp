@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "../csrc/bam_mod_rules.h"
 #include "../csrc/bam_out_rules.h"
 #include "../csrc/bam_tag_rules.h"
 
@@ -13,6 +14,7 @@ namespace fplh {
 
 namespace rule = fpl::bamout;
 namespace tagrule = fpl::bamtag;
+namespace modrule = fpl::bammod;
 
 namespace {
 /* magic, l_text, the text, n_ref = 0 */
@@ -31,14 +33,90 @@ struct MemScan {
         return z ? (uint64_t)((const uint8_t*)z - v) + 1 : 0;
     }
 };
-/* what the rule picks of the input record at rec, appended to out -> the bytes appended */
-uint64_t append_tags(const uint8_t* rec, bool changed, std::string& out, uint64_t* stats) {
+void put32(std::string& out, uint32_t v) {
+    for (int b = 0; b < 4; b++) out += (char)(v >> (8 * b));
+}
+/* --keep_mods: the fields of a changed record of the re-indexable record R (csrc/bam_mod_rules.h), appended to out: the
+   non-positional fields verbatim, the three modification fields rewritten for s's range, in the fields' order.  lost: another
+   positional field was dropped; mod_stats[2], [3]: positions kept, cut away */
+void append_reindexed(const BamTagSrc& s, const uint8_t* p, uint64_t prefix, const modrule::Record& R, std::string& out, bool& lost,
+                      uint64_t* mod_stats) {
+    const fpl::bamrule::Fields f = fpl::bamrule::fields(s.rec);
+    const uint8_t* pk = s.rec + fpl::bamrule::qual_offset(f) - ((uint64_t)f.l_seq + 1) / 2;
+    const uint8_t* v = p + R.fd.mm_at + 3;
+    const uint32_t v_len = (uint32_t)(R.fd.mm_len - 4);
+    const uint64_t a = std::min<uint64_t>(s.start, f.l_seq), b = std::min<uint64_t>((uint64_t)s.start + s.len, f.l_seq);
+    uint64_t c0[5], c1[5];
+    bool have[5] = {false, false, false, false, false};
+    modrule::Cut cuts[modrule::MAX_GROUPS];
+    uint64_t n_ml = 0;
+    for (uint32_t k = 0; k < R.n_groups; k++) {
+        const modrule::Group& g = R.g[k];
+        const uint32_t slot = modrule::code_slot(g.code);
+        if (!have[slot]) c0[slot] = modrule::count_bases(pk, a, g.code), c1[slot] = modrule::count_bases(pk, b, g.code), have[slot] = true;
+        cuts[k] = modrule::cut(v, v_len, g, c0[slot], c1[slot]);
+        n_ml += (uint64_t)(cuts[k].j1 - cuts[k].j0) * g.k;
+        if (mod_stats) mod_stats[2] += cuts[k].j1 - cuts[k].j0, mod_stats[3] += g.n_delta - (cuts[k].j1 - cuts[k].j0);
+    }
+    lost = false;
+    for (uint64_t o = 0; o < prefix;) {
+        const uint64_t n = tagrule::field_len(p + o, prefix - o, MemScan());
+        const char* fp = (const char*)p + o;
+        if (o == R.fd.mm_at) {
+            out.append(fp, 3);
+            for (uint32_t k = 0; k < R.n_groups; k++) {
+                out.append((const char*)v + R.g[k].at, R.g[k].hdr_len);
+                if (cuts[k].j1 > cuts[k].j0) {
+                    out += ',';
+                    out += std::to_string(cuts[k].first);
+                    out.append((const char*)v + cuts[k].rest_at, cuts[k].rest_end - cuts[k].rest_at);
+                }
+                out += ';';
+            }
+            out += '\0';
+        } else if (o == R.fd.ml_at) {
+            out.append(fp, 4);
+            put32(out, (uint32_t)n_ml);
+            for (uint32_t k = 0; k < R.n_groups; k++)
+                out.append(fp + 8 + R.g[k].ml_at + (uint64_t)cuts[k].j0 * R.g[k].k, (size_t)(cuts[k].j1 - cuts[k].j0) * R.g[k].k);
+        } else if (R.fd.n_mn && o == R.fd.mn_at) {
+            out.append(fp, 3);
+            const uint64_t len = b - a;
+            for (uint64_t k = 0; k + 3 < n; k++) out += (char)(len >> (8 * k));
+        } else if (!tagrule::positional(p + o))
+            out.append(fp, (size_t)n);
+        else
+            lost = true;
+        o += n;
+    }
+}
+/* what the rules pick of the input record of s, appended to out -> the bytes appended */
+uint64_t append_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats) {
+    const uint8_t* rec = s.rec;
+    const bool changed = s.changed;
     uint64_t at, len;
     tagrule::region(rec, at, len);
     const uint8_t* p = rec + at;
     const tagrule::Walk w = tagrule::walk(p, len, MemScan());
     uint64_t wrote = w.prefix;
-    if (!changed || !w.positional) {
+    bool lost = changed && w.positional;
+    bool done = false;
+    if (s.mods && changed) {
+        const modrule::Found fd = modrule::find(p, w.prefix, MemScan());
+        if (modrule::any_found(fd)) {
+            modrule::Record R;
+            if (modrule::reindexable(rec, p, fd, s.fragment_mode, R)) {
+                const size_t before = out.size();
+                append_reindexed(s, p, w.prefix, R, out, lost, mod_stats);
+                wrote = out.size() - before;
+                done = true;
+                if (mod_stats) mod_stats[0]++;
+            } else if (mod_stats)
+                mod_stats[1]++;
+        }
+    }
+    if (done) {
+    } else if (!changed || !w.positional) {
         out.append((const char*)p, (size_t)w.prefix);
     } else { /* the non-positional fields, in their order */
         wrote = w.kept;
@@ -49,7 +127,7 @@ uint64_t append_tags(const uint8_t* rec, bool changed, std::string& out, uint64_
         }
     }
     if (stats) {
-        stats[changed && w.positional ? 1 : 0]++;
+        stats[lost ? 1 : 0]++;
         stats[2] += wrote;
         if (!w.whole) stats[3]++;
     }
@@ -83,7 +161,7 @@ size_t fastq_record_count(const std::string& text) {
 
 void fastq_to_bam_records(const std::string& text, std::string& out) { fastq_to_bam_records(text, nullptr, 0, out, nullptr); }
 
-void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats) {
+void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats, uint64_t* mod_stats) {
     size_t k = 0; /* the record's place in the text */
     static const struct Table {
         uint8_t t[256];
@@ -128,7 +206,7 @@ void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t 
         for (uint32_t i = 0; i < n_q; i++) d[i] = (uint8_t)rule::qual_code(qual[i]);
         for (uint32_t i = n_q; i < l_seq; i++) d[i] = 0;
         if (k < n_src && src[k].rec) { /* (d is no use behind this: out grows) */
-            const uint64_t bs = rule::record_len(nl, l_seq) - 4u + append_tags(src[k].rec, src[k].changed, out, stats);
+            const uint64_t bs = rule::record_len(nl, l_seq) - 4u + append_tags(src[k], out, stats, mod_stats);
             for (int b = 0; b < 4; b++) out[at + (size_t)b] = (char)(bs >> (8 * b));
         }
         k++;

@@ -6,6 +6,9 @@
  * --keep_tags: the header also carries the input's @RG lines, and a record the auxiliary fields of the input record its read
  * came from, picked by csrc/bam_tag_rules.h.  Which input record that is the text does not say: the caller names it, record by
  * record in the text's order (host/bam_tags.h derives the list from a batch's results).
+ *
+ * --keep_mods: a changed record of a re-indexable input record (csrc/bam_mod_rules.h) gets its MM / ML / MN fields rewritten for
+ * its piece of the read in place of losing them.
  */
 #ifndef FPLH_BAM_OUT_H
 #define FPLH_BAM_OUT_H
@@ -33,11 +36,19 @@ void fastq_to_bam_records(const std::string& text, std::string& out);
 struct BamTagSrc {
     const uint8_t* rec;
     bool changed;
+    /* --keep_mods (csrc/bam_mod_rules.h): the record is the bases [start, start + len) of its read; mods: the switch is on;
+       fragment_mode: a --break / --mask run, in which no record is re-indexable */
+    uint32_t start = 0, len = 0;
+    bool mods = false, fragment_mode = false;
+    BamTagSrc(const uint8_t* r, bool c) : rec(r), changed(c) {}
+    BamTagSrc(const uint8_t* r, bool c, uint32_t s, uint32_t n, bool m, bool fm) : rec(r), changed(c), start(s), len(n), mods(m), fragment_mode(fm) {}
 };
 /* the same with tags: record k of the text gets what the rule picks of src[k] (k >= n_src: nothing).  stats (4 counts, added to):
    records that kept every field of their parsed prefix, records that lost positional fields, tag bytes written, records whose
-   region did not parse to its end */
-void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats);
+   region did not parse to its end.  mod_stats (4 counts, added to; only sources with `mods` move them): records re-indexed, changed
+   records whose modification fields were not re-indexable and went the old way, modification positions kept, positions cut away */
+void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats,
+                          uint64_t* mod_stats = nullptr);
 /* records of a formatted text: a quarter of its line ends */
 size_t fastq_record_count(const std::string& text);
 

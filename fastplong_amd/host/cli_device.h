@@ -43,6 +43,9 @@ struct DeviceApi {
     typedef int (*BamTagStatsFn)(fpl_ctx*, uint64_t*);
     SetGzipFn set_bam_tags = nullptr;
     BamTagStatsFn get_bam_tag_stats = nullptr;
+    /* --keep_mods: ... and re-index MM / ML / MN in them (found by name; without them the host writes every record of such a run) */
+    SetGzipFn set_bam_mods = nullptr;
+    BamTagStatsFn get_bam_mod_stats = nullptr;
 };
 
 static DeviceApi load_device_api() {
@@ -61,6 +64,8 @@ static DeviceApi load_device_api() {
     a.set_gzip_records = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_gzip_records");
     a.set_bam_tags = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_tags");
     a.get_bam_tag_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_tag_stats");
+    a.set_bam_mods = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_mods");
+    a.get_bam_mod_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_mod_stats");
     return a;
 }
 

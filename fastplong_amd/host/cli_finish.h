@@ -45,6 +45,17 @@ static void print_pipeline_summary(const Pipeline& p) {
         cerr << "BAM tags: " << t[0] << " records kept every field, " << t[1] << " lost positional fields (MM, ML, MN, B arrays), " << t[2]
              << " bytes" << endl;
     }
+    if (p.opt.keepMods) { /* the same two forms */
+        uint64_t t[4];
+        for (int k = 0; k < 4; k++) t[k] = g_bamModStats[k].load();
+        for (fpl_ctx* ctx : p.ctxs) {
+            uint64_t c[4] = {0, 0, 0, 0};
+            if (p.api.get_bam_mod_stats && p.api.get_bam_mod_stats(ctx, c) == FPL_OK)
+                for (int k = 0; k < 4; k++) t[k] += c[k];
+        }
+        cerr << "BAM modifications: " << t[0] << " records re-indexed, " << t[1] << " not re-indexable and dropped, " << t[2]
+             << " positions kept, " << t[3] << " cut away" << endl;
+    }
     if (in.textMode)
         cerr << "device parse: " << p.nTextBatches.load() << " chunks parsed on the device, " << p.nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;

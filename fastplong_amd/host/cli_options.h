@@ -81,7 +81,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""},
 };
 
 struct Args {
@@ -171,6 +171,7 @@ struct Options {
     int readerThreads = 0, compression = 0;
     bool gzStream = false, deviceParse = false, hostParse = false, hostGzip = false, deviceGzip = false, deviceInflate = false;
     bool bgzf = false; /* --bgzf: every .gz this run writes is BGZF blocks plus the EOF block */
+    bool keepMods = false; /* --keep_mods: with --keep_tags, a trimmed or split record's MM / ML / MN are re-indexed, not dropped (csrc/bam_mod_rules.h) */
     bool keepTags = false; /* --keep_tags: BAM input's auxiliary fields and @RG lines go into the .bam outputs (README "BAM output") */
     string command; /* src/main.cpp:252-256 */
     time_t t1 = 0;
@@ -333,6 +334,8 @@ static Options parse_options(int argc, char** argv) {
         error_exit("--bgzf needs an output whose name ends in .gz (--out, --failed_out or the --split files)");
     p.keepTags = cmd.exist("keep_tags");
     if (p.keepTags && !bamOut) error_exit("--keep_tags needs an output whose name ends in .bam (--out or --failed_out)");
+    p.keepMods = cmd.exist("keep_mods");
+    if (p.keepMods && !p.keepTags) error_exit("--keep_mods needs --keep_tags");
     if (p.splitEnabled && ends_with_bam(p.out)) error_exit("--split / --split_by_lines do not write BAM files (--out " + p.out + ")");
 
     stringstream ss; /* src/main.cpp:252-256 */

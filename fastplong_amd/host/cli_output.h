@@ -106,10 +106,13 @@ struct OutFile {
 
 /* --keep_tags: what the host's converter counted (bam_out.h), over every formatter thread */
 static std::atomic<uint64_t> g_bamTagStats[4];
+/* --keep_mods: the same for its four counts */
+static std::atomic<uint64_t> g_bamModStats[4];
 
 struct Outputs {
     OutFile fout, ffail;
     bool keepTags = false; /* --keep_tags: a .bam output's records carry their input record's auxiliary fields */
+    bool keepMods = false; /* --keep_mods: ... with MM / ML / MN re-indexed where the record is trimmed or split */
     int gzLevel = 4;
     bool bgzf = false; /* --bgzf: the pieces are framed by bgzf_into */
     fplh::SplitOutput* split = nullptr; /* --split / --split_by_lines: the workers' private writers take the passing reads */
@@ -122,9 +125,9 @@ struct Outputs {
         const int level = gzLevel;
         const bool blocks = file.bgzf, records = file.bam;
         if (records && tags) {
-            uint64_t st[4] = {0, 0, 0, 0};
-            fplh::pieces_to_bam_records(pieces, *tags, st);
-            for (int k = 0; k < 4; k++) g_bamTagStats[k] += st[k];
+            uint64_t st[4] = {0, 0, 0, 0}, ms[4] = {0, 0, 0, 0};
+            fplh::pieces_to_bam_records(pieces, *tags, st, ms);
+            for (int k = 0; k < 4; k++) g_bamTagStats[k] += st[k], g_bamModStats[k] += ms[k];
         }
         fplh::parallel_run((int)pieces.size(), [&](int i) {
             if (pieces[i].empty()) return;
@@ -153,6 +156,7 @@ static Outputs open_outputs(const Options& opt, const string& bamReadGroups = st
     if (opt.toStdout) o.fout.f = stdout, o.fout.gz = false, o.fout.bgzf = false, o.fout.bam = false, o.fout.positional = false;
     o.gzLevel = min(9, max(1, opt.compression));
     o.keepTags = opt.keepTags;
+    o.keepMods = opt.keepMods;
     o.fout.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     o.ffail.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     if (opt.splitEnabled)

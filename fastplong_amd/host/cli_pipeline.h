@@ -292,8 +292,11 @@ void Pipeline::enable_device_gzip() {
     const bool bamOut = out.fout && out.fout.bam;
     /* --keep_tags: the device form needs fpl_set_bam_tags besides; against a library without it the host writes every record */
     if (bamOut && opt.keepTags) eligible = eligible && api.set_bam_tags != nullptr;
+    /* --keep_mods: ... and fpl_set_bam_mods, in the same way */
+    if (bamOut && opt.keepMods) eligible = eligible && api.set_bam_mods != nullptr;
     if (bamOut) eligible = eligible && opt.deviceGzip && (in.textMode || facts.bam) && (devBamOut = frame_on_all(api.set_gzip_records, ctxs));
-    if (bamOut && opt.keepTags && devBamOut && !enable_on_all(api.set_bam_tags, true, ctxs)) { /* (a context refused: the host's form) */
+    if (bamOut && opt.keepTags && devBamOut &&
+        !(enable_on_all(api.set_bam_tags, true, ctxs) && (!opt.keepMods || enable_on_all(api.set_bam_mods, true, ctxs)))) { /* (a context refused: the host's form) */
         for (fpl_ctx* c : ctxs) (void)api.set_gzip_records(c, FPL_GZIP_FASTQ);
         eligible = devBamOut = false;
     }
@@ -703,8 +706,8 @@ void Pipeline::format_stage(int f) {
             /* --keep_tags: which input record every record of the pieces came from, by the formatter's own order */
             const fplh::FragmentList* fl = opt.fragmentMode ? &w->frags : nullptr;
             const bool tagOut = out.keepTags && out.fout && out.fout.bam && !w->dev_gz, tagFailed = out.keepTags && toFailed && out.ffail.bam;
-            if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags);
-            if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags);
+            if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, out.keepMods);
+            if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, out.keepMods);
             if (w->dev_gz) { /* (formatted for --failed_out alone) */
                 w->outs.resize(1);
                 w->outs[0].swap(w->gz_member);

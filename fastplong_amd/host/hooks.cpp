@@ -96,6 +96,46 @@ int format_hook(void* bv, const fpl_read_result* res, const fplh::FragmentList* 
     if (failed) hand_out(ff, failed, failed_len);
     return 0;
 }
+/* the host form as the CLI runs it: the BAM file at `path` read into ONE batch (BamReader), its decoded bases and qualities and
+   its results (and, with n_frags != ~0u, the fragment list of a --break / --mask run) given by the caller; formatted in `threads`
+   pieces, the sources derived (bam_tag_sources), the pieces converted (pieces_to_bam_records).  out / failed: the uncompressed
+   records of --out / --failed_out; stats: four counts each.  -1: the file did not read to its end as one batch of n reads.
+   mods: --keep_mods, with its four counts each in mod_stats */
+int bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n, const fpl_fragment* frags,
+                 uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out, uint64_t* out_len, char** failed,
+                 uint64_t* failed_len, uint64_t* stats, bool mods, uint64_t* mod_stats) {
+    fplh::BamReader rd(path);
+    if (!rd.ok()) return -1;
+    Batch b;
+    if (rd.fill(b, ~0ull, 0x3FFFFFFFu) != n || !rd.error().empty() || b.n() != n) return -1;
+    if (b.seq.size()) {
+        memcpy(b.seq.data(), seq, b.seq.size());
+        memcpy(b.qual.data(), qual, b.seq.size());
+    }
+    fplh::FragmentList fl;
+    const bool fragments = n_frags != ~0u;
+    if (fragments) {
+        fl.frags.assign(frags, frags + n_frags);
+        fl.regs.assign(regs, regs + n_regs);
+        fl.index(n);
+    }
+    std::vector<std::string> o, f;
+    fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
+    std::vector<fplh::BamTagSrc> so, sf;
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so, mods);
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf, mods);
+    for (int k = 0; k < 8; k++) stats[k] = 0;
+    if (mod_stats)
+        for (int k = 0; k < 8; k++) mod_stats[k] = 0;
+    fplh::pieces_to_bam_records(o, so, stats, mod_stats);
+    fplh::pieces_to_bam_records(f, sf, stats + 4, mod_stats ? mod_stats + 4 : nullptr);
+    std::string oo, ff;
+    for (auto& x : o) oo += x;
+    for (auto& x : f) ff += x;
+    hand_out(oo, out, out_len);
+    hand_out(ff, failed, failed_len);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -255,42 +295,16 @@ void fplh_bam_tag_walk(const uint8_t* p, uint64_t len, uint64_t* out) {
     out[0] = w.prefix, out[1] = w.kept, out[2] = w.positional, out[3] = w.whole;
 }
 void fplh_bam_tag_region(const uint8_t* rec, uint64_t* at, uint64_t* len) { fpl::bamtag::region(rec, *at, *len); }
-/* the host form as the CLI runs it: the BAM file at `path` read into ONE batch (BamReader), its decoded bases and qualities and
-   its results (and, with n_frags != ~0u, the fragment list of a --break / --mask run) given by the caller; formatted in `threads`
-   pieces, the sources derived (bam_tag_sources), the pieces converted (pieces_to_bam_records).  out / failed: the uncompressed
-   records of --out / --failed_out; stats: four counts each.  -1: the file did not read to its end as one batch of n reads */
+/* the host form as the CLI runs it (bam_tag_form above); _mod_form: with --keep_mods, and its four counts each in mod_stats */
 int fplh_bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n,
                       const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
                       uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats) {
-    fplh::BamReader rd(path);
-    if (!rd.ok()) return -1;
-    Batch b;
-    if (rd.fill(b, ~0ull, 0x3FFFFFFFu) != n || !rd.error().empty() || b.n() != n) return -1;
-    if (b.seq.size()) {
-        memcpy(b.seq.data(), seq, b.seq.size());
-        memcpy(b.qual.data(), qual, b.seq.size());
-    }
-    fplh::FragmentList fl;
-    const bool fragments = n_frags != ~0u;
-    if (fragments) {
-        fl.frags.assign(frags, frags + n_frags);
-        fl.regs.assign(regs, regs + n_regs);
-        fl.index(n);
-    }
-    std::vector<std::string> o, f;
-    fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
-    std::vector<fplh::BamTagSrc> so, sf;
-    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so);
-    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf);
-    for (int k = 0; k < 8; k++) stats[k] = 0;
-    fplh::pieces_to_bam_records(o, so, stats);
-    fplh::pieces_to_bam_records(f, sf, stats + 4);
-    std::string oo, ff;
-    for (auto& x : o) oo += x;
-    for (auto& x : f) ff += x;
-    hand_out(oo, out, out_len);
-    hand_out(ff, failed, failed_len);
-    return 0;
+    return bam_tag_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, out, out_len, failed, failed_len, stats, false, nullptr);
+}
+int fplh_bam_mod_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n,
+                      const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
+                      uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats, uint64_t* mod_stats) {
+    return bam_tag_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, out, out_len, failed, failed_len, stats, true, mod_stats);
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */

@@ -504,6 +504,29 @@ int fpl_set_bam_tags(fpl_ctx* ctx, int on);
 int fpl_get_bam_tag_stats(fpl_ctx* ctx, uint64_t* out);
 
 /*
+ * MM / ML / MN re-indexed in such records where they are trimmed or split (README "BAM output", --keep_mods; the rule and its
+ * wording: csrc/bam_mod_rules.h).  FPL_ABI_VERSION stays 10: both calls are found by symbol lookup; a caller of a library
+ * without them writes such records on the host.
+ *
+ *   fpl_set_bam_mods   per context; takes effect with the NEXT submission and is ignored unless fpl_set_bam_tags is on.  A changed
+ *                      output record -- one that does not get its prefix verbatim -- of a RE-INDEXABLE input record gets, in the
+ *                      places of its MM, ML and MN fields, those fields rewritten for its bases [frag_start, + frag_len) of the
+ *                      read: per group the deltas that fall on a base of the fragment, the first of them counted from the
+ *                      fragment's first base, their ML values, MN = frag_len.  Every other positional field is dropped as before.
+ *                      Re-indexable: flag without 0x10, no --break / --mask, exactly one MM (or Mm) of type Z and one ML (Ml) of
+ *                      type B:C, at most one integer MN (Mn) that equals l_seq, an MM value of at most 16 well-formed groups whose
+ *                      deltas (1 to 9 digits) do not run past the read's count of the group's base, an ML count that matches.  A
+ *                      record with such fields that is not re-indexable is written as without the switch.  A record's tag bytes
+ *                      never exceed its input region: the bound of fpl_set_bam_tags stands.
+ *   fpl_get_bam_mod_stats   out[4], since the context was made: output records re-indexed; changed output records whose
+ *                      modification fields were not re-indexable and were dropped; modification positions kept; positions cut
+ *                      away.  It waits like fpl_get_bam_tag_stats, whose counts keep their meaning: a re-indexed record that lost
+ *                      no other positional field counts as one that kept every field.
+ */
+int fpl_set_bam_mods(fpl_ctx* ctx, int on);
+int fpl_get_bam_mod_stats(fpl_ctx* ctx, uint64_t* out);
+
+/*
  * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
  * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
  * caller then inflates on the host.

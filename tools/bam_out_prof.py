@@ -6,7 +6,13 @@ SESSION; with it the records' form (Engine.set_gzip_records).
 
 Bytes k_bamout_compose moves per base: 2 read (base, quality), 1.5 written = 3.5; the roofline printed is that count at 8 TB/s,
 next to the whole design's (compose as above, k_gz_block_bgzf reads the 1.5 and writes the coded block, k_gz_compact reads and
-writes that again).  The wall time printed holds the upload, the parse, the per-read kernels and the bytes' way back as well."""
+writes that again).  The wall time printed holds the upload, the parse, the per-read kernels and the bytes' way back as well.
+
+`--mods [Mbases]` / `--mods --tags-only [Mbases]`: the --keep_mods leg (fastplong_amd/csrc/bam_mods.h).  A resident BAM batch of
+ONT-like reads with adapters (median 5 kb, a middle adapter in three of ten) that carry generated modification calls -- C+mh? at
+CpGs, A+a. at every fourth A, a sparse N+n group --, submitted three times through Engine.submit_bam(gzip=True) with set_bam_tags
+and set_bam_mods (k_bam_tags_mods, k_bam_mods_plan, k_bamout_compose_bam_mods), or with --tags-only with set_bam_tags alone
+(k_bam_tags, k_bamout_compose_bam_tags): the form to compare with in the same session."""
 import os
 import sys
 import time
@@ -54,6 +60,50 @@ def main(mbases=1000, L=10_000, bam=False):
     eng.close()
 
 
+def mods_main(mbases=100, mods=True):
+    from fastplong_amd import synth
+    from tests import bam_mod_cases as mc
+    from tests import bamio, hostio
+    L = 5000
+    pool = 256  # distinct reads: generating the calls in Python is the slow part; the kernels do not care that reads repeat
+    rng = np.random.default_rng(2)
+    seq, qual, off = synth.ont_like(pool, seed=3, median_len=L, p_middle=0.3)
+    encoded = []
+    for i, (_, _, codes, q) in enumerate(bamio.fastq_to_records(hostio.make_fastq(seq, qual, off)[0])):
+        occ = mc.occurrences(codes, b"C")
+        cpg = [k for k, p in enumerate(occ) if p + 1 < len(codes) and codes[p + 1] == 4]
+        spec = [(b"C+mh?", [m - (cpg[j - 1] + 1 if j else 0) for j, m in enumerate(cpg)]), (b"A+a.", mc.every(codes, b"A", 4, 3)),
+                (b"N+n", mc.every(codes, b"N", 997, 11))]
+        encoded.append((len(codes), bamio.encode_record(b"read%d" % i, 4, codes, q, tags=mc.fields_of(codes, spec, rng))))
+    n = max(1, mbases * 1_000_000 // L)
+    raw, starts, offs = bytearray(), [], [0]
+    for i in range(n):
+        starts.append(len(raw))
+        offs.append(offs[-1] + encoded[i % pool][0])
+        raw += encoded[i % pool][1]
+    starts, offs = np.array(starts, np.uint64), np.array(offs, np.uint64)
+    eng = engine.Engine(abi.FplOptions.default(cut_front=1, cut_tail=1, cut_front_window=5, cut_tail_window=5), synth.START_ADAPTER,
+                        synth.END_ADAPTER, device=0, max_cycles=int(max(e[0] for e in encoded)) + 64)
+    eng.set_gzip_records(True)
+    eng.set_bam_tags(True)
+    eng.set_bam_mods(mods)
+    buf = eng.pinned_array(len(raw))
+    buf[:] = np.frombuffer(bytes(raw), np.uint8)
+    res = np.zeros(n, abi.RESULT_DTYPE)
+    for k in range(3):
+        t0 = time.time()
+        eng.submit_bam(buf, starts, offs, res=res, gzip=True)
+        out = eng.wait()
+        print("batch %d (%s): %.3f s wall, %d records of %d bytes, %.3f Gbases -> %d bytes of BGZF blocks; %d split reads" % (
+            k, "--keep_mods" if mods else "--keep_tags alone", time.time() - t0, n, len(raw), int(offs[-1]) / 1e9, len(out), int((res["n_frag"] == 2).sum())))
+    print("tag counts: %s; modification counts: %s" % (eng.bam_tag_stats(), eng.bam_mod_stats()))
+    eng.close()
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--bam"]
-    main(*(int(a) for a in args[:1]), bam="--bam" in sys.argv[1:])
+    flags = ("--bam", "--mods", "--tags-only")
+    args = [a for a in sys.argv[1:] if a not in flags]
+    if "--mods" in sys.argv[1:]:
+        mods_main(*(int(a) for a in args[:1]), mods="--tags-only" not in sys.argv[1:])
+    else:
+        main(*(int(a) for a in args[:1]), bam="--bam" in sys.argv[1:])
