@@ -196,13 +196,16 @@ inline u32 cdiv(u32 a, u32 b) { return (a + b - 1) / b; }
  * 14-bit counter fields allow; measured optimum: ~1.25 heavy blocks per block slot of the chip (2 per CU). */
 inline u32 stats_items_per_slice(u32 n_items, u32 mean_len, u32 n_cu, const StatsTune& tune) {
     if (n_items == 0) return 64;
-    if (tune.per) return tune.per;
+    constexpr u32 per_max = CS_MAX_ITEMS_PER_SLICE / 64 * 64;
+    /* (the hook keeps what the rule below keeps: a multiple of 64 -- k_bucket_plan sizes a bucket's slices by it -- that the
+       14-bit fields hold) */
+    if (tune.per) return tune.per >= per_max ? per_max : (tune.per + 63) / 64 * 64;
     const u32 heavy_tiles = mean_len / FS_T + 1;
     const u32 slices = cdiv(5 * n_cu / 2, heavy_tiles);
     u32 per = cdiv(n_items, slices);
     per = (per + 63) / 64 * 64;
     if (per < 1024) per = 1024;
-    if (per > CS_MAX_ITEMS_PER_SLICE / 64 * 64) per = CS_MAX_ITEMS_PER_SLICE / 64 * 64;
+    if (per > per_max) per = per_max;
     return per;
 }
 /* EXTRA pass (post-only fragments; count known only on the device): a fixed number of blocks per tile walk

@@ -136,6 +136,20 @@ extern "C" int emu_process_batch(const fpl_options* opt, const char* start, int 
     return 0;
 }
 
+/* the host rules that size the statistics passes (pipeline.h), for a batch of n_reads reads of mean_len bases each on n_cu CUs, with
+   the hooks FPL_STATS_PER / FPL_STATS_MIN_BUCKET as given (0: the built-in choice) -> out[0] reads per slice, out[1] the bound of
+   the sorted pass's slices, out[2] the slabs of the scratch buffer */
+extern "C" void emu_stats_slice_rule(uint32_t n_reads, uint32_t mean_len, uint32_t n_cu, uint32_t per_hook, uint32_t min_bucket_hook,
+                                     uint64_t* out) {
+    StatsTune t;
+    t.per = per_hook;
+    t.min_bucket = min_bucket_hook;
+    const u32 per = stats_items_per_slice(n_reads, mean_len, n_cu, t);
+    out[0] = per;
+    out[1] = stats_sorted_max_slices(n_reads, per, t);
+    out[2] = stats_scratch_slabs(n_reads, (uint64_t)n_reads * mean_len, mean_len, n_cu, t);
+}
+
 /* k_count_end_kmers (the counting of the adapter auto-detection) on the emulator: counts / position_acc of 4^10 entries */
 extern "C" void emu_count_end_kmers(const uint8_t* seq, const uint64_t* off, uint32_t n_reads, int side, int shift_tail,
                                     uint32_t* counts, unsigned long long* position_acc, unsigned long long* total) {

@@ -4,25 +4,20 @@
 For every entry of MUTANTS: copy the tree's sources to a temporary directory, apply the entry's edits to fastplong_amd/csrc/kernels.h there
 (each search text must occur exactly as often as the entry says: a stale entry fails loudly), run ONLY tests/test_scan_emu.py in
 the copy -- the emulator library builds itself from the mutated header -- and report: survived, or killed and by what (a failed
-assertion, a crash of the emulator, a time-out) and in which test first.  Exit status 0 when every mutant was killed by an
-assertion.
+assertion, a crash of the emulator, a time-out) and in which test first (tools/mutant_runner.py, shared with tools/stats_mutants.py).
+Exit status 0 when every mutant was killed by an assertion.
 
     python tools/scan_mutants.py [-j JOBS] [--only NAME ...] [-k EXPR] [--markdown] [--with-crashing]
 
 docs/kernels.md ("Directed tests for the middle-adapter scan") holds the table this prints with --markdown."""
-import argparse
-import concurrent.futures
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
-import xml.etree.ElementTree as ET
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mutant_runner  # noqa: E402
+
 HEADER = os.path.join("fastplong_amd", "csrc", "kernels.h")
 TESTS = os.path.join("tests", "test_scan_emu.py")
-TIMEOUT = 900
 
 # name, what it does, [(search text, replacement, number of sites)]
 MUTANTS = [
@@ -90,74 +85,19 @@ CRASHING = [
      [MUTANTS[7][2][0]]),
 ]
 
-NEEDED = ("fastplong_amd", "tests", "oracle", "include")  # what the emulator tests read: the sources, not what was built from them
-SKIP = shutil.ignore_patterns("__pycache__", ".pytest_cache", "_ref", "*.so", "*.o", "*.tmp.*")
 
-
-SELECT = []  # pytest -k expression, when given
-
-
-def run_mutant(entry):
-    name, what, edits = entry
-    with tempfile.TemporaryDirectory(prefix="scan_mutant_%s_" % name) as tmp:
-        tree = os.path.join(tmp, "tree")
-        for d in NEEDED:
-            shutil.copytree(os.path.join(ROOT, d), os.path.join(tree, d), ignore=SKIP, symlinks=True)
-        path = os.path.join(tree, HEADER)
-        with open(path) as f:
-            text = f.read()
-        for search, repl, sites in edits:
-            found = text.count(search)
-            assert found == sites, "%s: %r occurs %d times in %s, not %d: the entry is stale" % (name, search, found, HEADER, sites)
-            text = text.replace(search, repl)
-        with open(path, "w") as f:
-            f.write(text)
-        env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-        report = os.path.join(tmp, "report.xml")
-        try:
-            p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "--junitxml=" + report, TESTS] + SELECT,
-                               cwd=tree, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=TIMEOUT)
-        except subprocess.TimeoutExpired:
-            return name, what, "time-out", ""
-        if p.returncode == 0:
-            return name, what, "SURVIVED", ""
-        if p.returncode < 0 or p.returncode > 128 or not os.path.exists(report):
-            return name, what, "crash (status %d)" % p.returncode, ""
-        # the first test that did not pass, and whether an assertion stopped it (not, say, a header that no longer compiles)
-        for case in ET.parse(report).getroot().iter("testcase"):
-            for kind in ("failure", "error"):
-                f = case.find(kind)
-                if f is not None:
-                    msg = f.get("message") or ""
-                    how = "assertion" if kind == "failure" and msg.startswith("AssertionError") else "error: " + msg[:80]
-                    return name, what, how, case.get("name")
-        return name, what, "error (status %d)" % p.returncode, ""
+def _entry(m):
+    """the runner's form of an entry: every edit names its file"""
+    return m[0], m[1], [(HEADER,) + e for e in m[2]]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("-j", "--jobs", type=int, default=max(1, min(8, (os.cpu_count() or 2) // 2)))
-    ap.add_argument("--only", nargs="*")
-    ap.add_argument("--markdown", action="store_true")
-    ap.add_argument("-k", dest="select", help="run only the tests of tests/test_scan_emu.py that match (pytest -k)")
+    ap = mutant_runner.arguments(TESTS)
     ap.add_argument("--with-crashing", action="store_true", help="also run CRASHING, which must be stopped by a crash")
     a = ap.parse_args()
-    if a.select:
-        SELECT[:] = ["-k", a.select]
-    todo = [m for m in MUTANTS if not a.only or m[0] in a.only]
-    with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
-        rows = list(ex.map(run_mutant, todo))
-    if a.markdown:
-        print("| mutant | what it breaks | stopped by | first test that fails |\n|---|---|---|---|")
-        for name, what, how, test in rows:
-            print("| `%s` | %s | %s | `%s` |" % (name, what, how, test))
-    else:
-        for name, what, how, test in rows:
-            print("%-13s %-28s %s" % (name, how, test))
-    bad = [r[0] for r in rows if r[2] != "assertion"]
-    print("%d mutants, %d killed by an assertion%s" % (len(rows), len(rows) - len(bad), "; NOT: " + " ".join(bad) if bad else ""))
+    bad = mutant_runner.run_table([_entry(m) for m in MUTANTS], TESTS, a)
     if a.with_crashing:
-        for name, what, how, test in map(run_mutant, CRASHING):
+        for name, what, how, test in (mutant_runner.run_mutant(_entry(m), TESTS) for m in CRASHING):
             print("%-13s %-28s %s   (expected: a crash)" % (name, how, test))
             if not how.startswith("crash"):
                 bad.append(name)
