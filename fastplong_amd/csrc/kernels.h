@@ -1889,7 +1889,7 @@ __device__ __forceinline__ bool lev_lanes_nw(const u8* __restrict__ text, int m,
 
 #ifdef FPL_EMU_TRIM_STATS
 static unsigned long long g_trim_stats[10]; /* emulator only: groups, lanes handed to P1b, P2 / P3 wants / P3 may, P6 / P7 wants / P7 may, lane-parallel partial searches / their rounds */
-#define FPL_TRIM_STAT(i, n) (g_trim_stats[i] += (unsigned long long)(n))
+#define FPL_TRIM_STAT(i, n) ((void)__atomic_fetch_add(&g_trim_stats[i], (unsigned long long)(n), __ATOMIC_RELAXED)) /* (one OS thread per wave) */
 #else
 #define FPL_TRIM_STAT(i, n) ((void)0)
 #endif

@@ -48,9 +48,9 @@ EMU = ["-pthread", "-Itests/emu"]
 SANITIZE = ["-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
-def emu_lib(out, src, module):
+def emu_lib(out, src, module, defines=()):
     """product kernels on the thread emulator (tests/emu/hip_emu.h) as a shared object that Python loads"""
-    return compile(out, ["-std=c++20", "-O1", "-g", "-fPIC", "-shared", *EMU], [src], extra_deps=[module])
+    return compile(out, ["-std=c++20", "-O1", "-g", "-fPIC", "-shared", *("-D" + d for d in defines), *EMU], [src], extra_deps=[module])
 
 
 def emu_program(out, src, module, main=None):

@@ -16,14 +16,38 @@ def build():
     return cbuild.emu_lib(LIB, "tests/emu/emu_driver.cpp", __file__)
 
 
+LIB_TRIM_STATS = os.path.join(HERE, "libfpl_emu_trimstats.so")
 _lib = None
+_libs = {}
+
+
+def use_trim_stats(on):
+    """switch process_batch to the build with the FPL_EMU_TRIM_STATS counters of kernels.h (a second cached library; it also
+    prints them per batch) and back"""
+    global _lib
+    _lib = None
+    _libs["want"] = LIB_TRIM_STATS if on else LIB
+
+
+def trim_stats():
+    """-> (groups of 64 reads k_trim_ends_batched took, reads it handed to its wave-per-read fallback) since the last call"""
+    out = (C.c_ulonglong * 2)()
+    assert lib().emu_trim_stats(out) == 0, "a counter is no multiple of 64 lanes"
+    return int(out[0]), int(out[1])
 
 
 def lib():
     global _lib
     if _lib is None:
-        build()
-        L = C.CDLL(LIB)
+        path = _libs.get("want", LIB)
+        if path in _libs:
+            _lib = _libs[path]
+            return _lib
+        if path == LIB:
+            build()
+        else:
+            cbuild.emu_lib(path, "tests/emu/emu_driver.cpp", __file__, defines=["FPL_EMU_TRIM_STATS"])
+        L = _libs[path] = C.CDLL(path)
         L.emu_process_batch.restype = C.c_int
         L.emu_process_batch.argtypes = [C.POINTER(abi.FplOptions), C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                         C.POINTER(abi.FplAdapter), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -136,6 +136,19 @@ extern "C" int emu_process_batch(const fpl_options* opt, const char* start, int 
     return 0;
 }
 
+#ifdef FPL_EMU_TRIM_STATS
+/* which path the end trims took, for tests/test_cut_emu.py (the build with the counters is a library of its own): out[0] = the groups
+   of 64 reads k_trim_ends_batched took, out[1] = the reads it handed to its wave-per-read fallback (P1b), counted since the last
+   call.  Every lane of a wave counts, so both are kept as multiples of 64 and divided here */
+extern "C" int emu_trim_stats(unsigned long long* out) {
+    const int whole = fpl::g_trim_stats[0] % 64 == 0 && fpl::g_trim_stats[1] % 64 == 0;
+    out[0] = fpl::g_trim_stats[0] / 64;
+    out[1] = fpl::g_trim_stats[1] / 64;
+    for (auto& v : fpl::g_trim_stats) v = 0;
+    return whole ? 0 : -1;
+}
+#endif
+
 /* the host rules that size the statistics passes (pipeline.h), for a batch of n_reads reads of mean_len bases each on n_cu CUs, with
    the hooks FPL_STATS_PER / FPL_STATS_MIN_BUCKET as given (0: the built-in choice) -> out[0] reads per slice, out[1] the bound of
    the sorted pass's slices, out[2] the slabs of the scratch buffer */
