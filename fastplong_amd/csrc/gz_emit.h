@@ -352,10 +352,15 @@ __device__ __forceinline__ void gz_wave_copy(u8* __restrict__ dst, const u8* __r
     if (lane < (len & 15u)) dst[whole + lane] = src[whole + lane];
 }
 
+/* what gz_compose_body writes behind fragment f's name, in front of the line's end (the whole wave calls it) -> where the line ends.
+   Nothing here; csrc/bam_comments.h has the form that writes a BAM record's fields as a comment */
+struct GzNoNote {
+    __device__ __forceinline__ u8* operator()(u32, int, u8* d) const { return d; }
+};
 /* a wave per record; comp holds hdr->total bytes (the caller sized it after k_gz_layout: comp_cap is checked all the same) */
-template <class Src>
+template <class Src, class Note = GzNoNote>
 __device__ __forceinline__ void gz_compose_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec,
-                                                const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+                                                const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap, const Note& note = Note()) {
     const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     const u32 lane = (u32)lane_id();
     for (u32 i = wave; i < n_rec; i += n_waves) { /* wave-uniform */
@@ -376,7 +381,7 @@ __device__ __forceinline__ void gz_compose_body(const Src& src, const fpl_read_r
                 }
                 gz_wave_copy(d + 1 + pl, g.name_rest, g.name_len - 1);
             }
-            d += g.name_len + pl;
+            d = note(i, f, d + g.name_len + pl);
             gz_wave_copy(d + 1, g.seq + fs, fl);
             u8* d2 = d + 1 + fl + 1;
             if (g.strand) gz_wave_copy(d2, g.strand, g.strand_len); /* (wave-uniform) */

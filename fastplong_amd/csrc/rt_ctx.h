@@ -133,6 +133,11 @@ struct fpl_ctx {
             DevBuf<BamModInfo> d_mod_info; /* k_bam_tags_mods -> k_bam_mods_plan and the compose kernel: one per input record */
             DevBuf<u32> d_mod_cand;        /* the candidate records */
             DevBuf<BamModPlan> d_mod_plan; /* one per candidate (sized for every record: how many there are only the device knows) */
+            /* ... or FASTQ text whose name lines carry the input records' fields as comments (fpl_set_bam_comments;
+               csrc/bam_comments.h): the selection when the batch was submitted (n 0: off) */
+            bamcomment::Selection notes = {};
+            DevBuf<u8> d_note_tags[2]; /* either fragment's tag bytes, at its record's place: each the size of the record buffer */
+            DevBuf<u64> d_note_len;    /* k_bam_comment_len -> the layout and compose kernels: two per input record */
         } gzip;
         /* a BAM batch: the inflated record bytes, where every record starts, and where the decoded bases go on the host (NULL: a
            gzip batch that leaves them on the device) */
@@ -179,6 +184,9 @@ struct fpl_ctx {
     bool gzip_records = false; /* fpl_set_gzip_records: the same */
     bool bam_tags = false;     /* fpl_set_bam_tags: the same */
     bool bam_mods = false;     /* fpl_set_bam_mods: the same */
+    bamcomment::Selection bam_comments = {}; /* fpl_set_bam_comments: the same (n 0: off) */
+    DevBuf<unsigned long long> d_note_counters; /* fpl_get_bam_comment_stats: four counts k_bam_comment_len adds to */
+    DevBuf<unsigned long long> d_note_work;     /* what k_bam_tags_mods / k_bam_mods_plan count for such a batch: nobody reads it but they (zeroed per batch) */
     DevBuf<unsigned long long> d_mod_counters; /* fpl_get_bam_mod_stats: four counts, and the candidates of the batch in flight (csrc/bam_mods.h) */
     DevBuf<unsigned long long> d_tag_counters; /* fpl_get_bam_tag_stats: four counts k_bam_tags adds to (made with the first tagged batch) */
     /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the

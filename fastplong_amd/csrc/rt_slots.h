@@ -41,9 +41,11 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
         FPL_HIP(g.h_hdr.alloc(1));
     }
     const bool tags = g.tags && g.records && bam; /* fpl_set_bam_tags: only where the bytes are BAM records of BAM records */
+    const bool notes = g.notes.n != 0 && !g.records && bam; /* fpl_set_bam_comments: only where the bytes are the FASTQ text of BAM records */
     const uint64_t blk_want = (g.records ? (bam ? bamout_bam_blocks_bound(sl.bam.bases, n) + (tags ? bamtag_extra_bound(sl.bam.bytes) / GZ_B + 1 : 0)
                                                 : bamout_blocks_bound(sl.text.bytes, n))
-                                         : (bam ? gz_bam_blocks_bound(sl.bam.bases, n) : gz_blocks_bound(sl.text.bytes, n))) + 1;
+                                         : (bam ? gz_bam_blocks_bound(sl.bam.bases, n) + (notes ? bamcomment_extra_bound(sl.bam.bytes) / GZ_B + 1 : 0)
+                                                : gz_blocks_bound(sl.text.bytes, n))) + 1;
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
     FPL_HIP(g.d_rec_off.grow((size_t)n + 1, 4096 / sizeof(u64)));
     if (!g.d_blk_start.holds(blk_want)) {
@@ -84,6 +86,37 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
                            (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, g.d_rec_off.ptr, g.d_blk_start.ptr,
                            blk_cap - 1, g.d_hdr.ptr);
+    } else if (notes) {
+        /* the walk and the plan of the tagged record form say which bytes either fragment's record would carry (their counts go
+           into a block nobody reads); the tails write those bytes out, a wave per record measures their text, then the layout */
+        if (!ctx->d_note_counters.ptr) {
+            FPL_HIP(ctx->d_note_counters.alloc(4));
+            FPL_HIP(hipMemsetAsync(ctx->d_note_counters.ptr, 0, 4 * sizeof(unsigned long long), st));
+            FPL_HIP(ctx->d_note_work.alloc(4 + BAMMOD_COUNTERS));
+        }
+        FPL_HIP(hipMemsetAsync(ctx->d_note_work.ptr, 0, (4 + BAMMOD_COUNTERS) * sizeof(unsigned long long), st));
+        FPL_HIP(g.d_tag_info.grow(n, 4096 / sizeof(BamTagInfo)));
+        FPL_HIP(g.d_mod_info.grow(n, 4096 / sizeof(BamModInfo)));
+        FPL_HIP(g.d_mod_cand.grow(n, 1024));
+        FPL_HIP(g.d_mod_plan.grow(n, 16));
+        FPL_HIP(g.d_note_len.grow(2 * (size_t)n, 4096 / sizeof(u64)));
+        for (auto& t : g.d_note_tags) FPL_HIP(t.grow((size_t)sl.bam.bytes + BAM_PAD, 4096));
+        const dim3 lanes(std::max<u32>(1u, std::min<u32>((n + 255) / 256, 8u * ctx->n_cu))), waves(std::max<u32>(1u, std::min<u32>((n + 3) / 4, 8u * ctx->n_cu)));
+        const u32 fragment_mode = (u32)(ctx->hcfg.defer ? 1 : 0);
+        hipLaunchKernelGGL(k_bam_tags_mods, lanes, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, ctx->d_note_work.ptr, g.d_mod_info.ptr,
+                           g.d_mod_cand.ptr, ctx->d_note_work.ptr + 4);
+        hipLaunchKernelGGL(k_bam_mods_plan, waves, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, (const BamModInfo*)g.d_mod_info.ptr,
+                           (const u32*)g.d_mod_cand.ptr, g.d_mod_plan.ptr, ctx->d_note_work.ptr, ctx->d_note_work.ptr + 4);
+        hipLaunchKernelGGL(k_bam_comment_tags, waves, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, (const BamModInfo*)g.d_mod_info.ptr,
+                           (const BamModPlan*)g.d_mod_plan.ptr, g.d_note_tags[0].ptr, g.d_note_tags[1].ptr);
+        hipLaunchKernelGGL(k_bam_comment_len, waves, dim3(256), 0, st, (const u8*)g.d_note_tags[0].ptr, (const u8*)g.d_note_tags[1].ptr, (u64)sl.bam.bytes,
+                           (const uint64_t*)sl.bam.d_rec.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, g.notes, g.d_note_len.ptr, ctx->d_note_counters.ptr);
+        hipLaunchKernelGGL(k_gz_layout_bam_comments, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
+                           (const u64*)g.d_note_len.ptr, g.d_rec_off.ptr, g.d_blk_start.ptr, blk_cap - 1, g.d_hdr.ptr);
     } else if (bam)
         hipLaunchKernelGGL(g.records ? k_bamout_layout_bam : k_gz_layout_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
                            (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
@@ -124,6 +157,11 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, (const u64*)g.d_rec_off.ptr,
                            g.d_comp.ptr, (u64)h.total);
+    else if (g.notes.n != 0 && !g.records && bam_records(sl.kind))
+        hipLaunchKernelGGL(k_gz_compose_bam_comments, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
+                           (const BamTagInfo*)g.d_tag_info.ptr, (const u8*)g.d_note_tags[0].ptr, (const u8*)g.d_note_tags[1].ptr,
+                           (const u64*)g.d_note_len.ptr, g.notes, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
     else if (bam_records(sl.kind))
         hipLaunchKernelGGL(g.records ? k_bamout_compose_bam : k_gz_compose_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
@@ -228,6 +266,7 @@ static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out
     sl.gzip.records = ctx->gzip_records;
     sl.gzip.tags = ctx->bam_tags;
     sl.gzip.mods = ctx->bam_tags && ctx->bam_mods;
+    sl.gzip.notes = ctx->bam_comments;
     sl.gzip.bgzf = ctx->gzip_bgzf || sl.gzip.records; /* BAM records are BGZF whatever the framing says (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
     sl.n_reads = 0;
     sl.user_results = nullptr;

@@ -136,6 +136,14 @@ int fpl_set_bam_mods(fpl_ctx* ctx, int on) {
     return FPL_OK;
 }
 
+int fpl_set_bam_comments(fpl_ctx* ctx, const char* tags, int n_tags) {
+    if (!ctx || (n_tags > 0 && !tags)) return FPL_ERR_ARG;
+    bamcomment::Selection s;
+    if (!bamcomment::make_selection(tags, n_tags, s)) return FPL_ERR_ARG;
+    ctx->bam_comments = s; /* (read by slot_begin, like the framing; a slot whose gzip bytes are not the FASTQ text of BAM records ignores it) */
+    return FPL_OK;
+}
+
 static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
                      const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;

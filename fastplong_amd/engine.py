@@ -27,6 +27,7 @@ EXPORTS = [
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing", "fpl_set_gzip_records",
     "fpl_set_bam_tags", "fpl_get_bam_tag_stats", "fpl_set_bam_mods", "fpl_get_bam_mod_stats",
+    "fpl_set_bam_comments", "fpl_get_bam_comment_stats",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
@@ -167,6 +168,11 @@ def load_library(path=None):
         L.fpl_set_bam_tags.argtypes = [C.c_void_p, C.c_int]
         L.fpl_get_bam_tag_stats.restype = C.c_int
         L.fpl_get_bam_tag_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "fpl_set_bam_comments"):  # (the same for Engine.set_bam_comments / bam_comment_stats)
+        L.fpl_set_bam_comments.restype = C.c_int
+        L.fpl_set_bam_comments.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.fpl_get_bam_comment_stats.restype = C.c_int
+        L.fpl_get_bam_comment_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     if hasattr(L, "fpl_set_bam_mods"):  # (the same for Engine.set_bam_mods / bam_mod_stats)
         L.fpl_set_bam_mods.restype = C.c_int
         L.fpl_set_bam_mods.argtypes = [C.c_void_p, C.c_int]
@@ -777,6 +783,33 @@ class Engine:
             raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_mod_stats")
         out = (C.c_uint64 * 4)()
         self._check(self.L.fpl_get_bam_mod_stats(self.h, out), "fpl_get_bam_mod_stats")
+        return tuple(int(v) for v in out)
+
+    def set_bam_comments(self, tags):
+        """fpl_set_bam_comments: the FASTQ text of the gzip batches submitted from now on (set_bam_gzip(True), submit_bam /
+        submit_bgzf, records as FASTQ) carries the auxiliary fields of its reads' input records as comments behind the names, by the
+        rule of README "Tags as FASTQ comments".  tags: None or an empty list for off, "*" for every field, or a list of up to 32
+        two-character tags (str or bytes)"""
+        if not hasattr(self.L, "fpl_set_bam_comments"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_bam_comments")
+        if tags is None:
+            raw, n = b"", 0
+        elif isinstance(tags, (str, bytes)) and tags in ("*", b"*"):
+            raw, n = b"", -1
+        else:
+            items = [t.encode() if isinstance(t, str) else bytes(t) for t in tags]
+            if any(len(t) != 2 for t in items):
+                raise FplError("fpl_set_bam_comments: a tag has two characters")
+            raw, n = b"".join(items), len(items)
+        self._check(self.L.fpl_set_bam_comments(self.h, raw, n), "fpl_set_bam_comments")
+
+    def bam_comment_stats(self):
+        """fpl_get_bam_comment_stats -> (output records that got at least one field, fields written, comment bytes with their tabs,
+        fields left out for control bytes), since the engine was made"""
+        if not hasattr(self.L, "fpl_get_bam_comment_stats"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_comment_stats")
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.fpl_get_bam_comment_stats(self.h, out), "fpl_get_bam_comment_stats")
         return tuple(int(v) for v in out)
 
     def gzip_batches(self):

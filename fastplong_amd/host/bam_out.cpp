@@ -90,8 +90,9 @@ void append_reindexed(const BamTagSrc& s, const uint8_t* p, uint64_t prefix, con
         o += n;
     }
 }
-/* what the rules pick of the input record of s, appended to out -> the bytes appended */
-uint64_t append_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats) {
+}  // namespace
+
+uint64_t bam_record_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats) {
     const uint8_t* rec = s.rec;
     const bool changed = s.changed;
     uint64_t at, len;
@@ -133,7 +134,6 @@ uint64_t append_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint
     }
     return wrote;
 }
-}  // namespace
 
 const std::string& bam_header_bytes() {
     static const std::string h = header_of(FPL_BAMOUT_HEADER_TEXT);
@@ -206,7 +206,7 @@ void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t 
         for (uint32_t i = 0; i < n_q; i++) d[i] = (uint8_t)rule::qual_code(qual[i]);
         for (uint32_t i = n_q; i < l_seq; i++) d[i] = 0;
         if (k < n_src && src[k].rec) { /* (d is no use behind this: out grows) */
-            const uint64_t bs = rule::record_len(nl, l_seq) - 4u + append_tags(src[k], out, stats, mod_stats);
+            const uint64_t bs = rule::record_len(nl, l_seq) - 4u + bam_record_tags(src[k], out, stats, mod_stats);
             for (int b = 0; b < 4; b++) out[at + (size_t)b] = (char)(bs >> (8 * b));
         }
         k++;

@@ -49,6 +49,9 @@ struct BamTagSrc {
    records whose modification fields were not re-indexable and went the old way, modification positions kept, positions cut away */
 void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats,
                           uint64_t* mod_stats = nullptr);
+/* what the rules pick of the input record of s (s.rec is not nullptr) -- the tag bytes of its output record --, appended to out
+   -> the bytes appended; stats, mod_stats: as above, nullptr for not wanted */
+uint64_t bam_record_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats);
 /* records of a formatted text: a quarter of its line ends */
 size_t fastq_record_count(const std::string& text);
 

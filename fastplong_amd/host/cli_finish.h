@@ -56,6 +56,16 @@ static void print_pipeline_summary(const Pipeline& p) {
         cerr << "BAM modifications: " << t[0] << " records re-indexed, " << t[1] << " not re-indexable and dropped, " << t[2]
              << " positions kept, " << t[3] << " cut away" << endl;
     }
+    if (p.opt.commentTags) { /* the same two forms */
+        uint64_t t[4];
+        for (int k = 0; k < 4; k++) t[k] = g_bamCommentStats[k].load();
+        for (fpl_ctx* ctx : p.ctxs) {
+            uint64_t c[4] = {0, 0, 0, 0};
+            if (p.api.get_bam_comment_stats && p.api.get_bam_comment_stats(ctx, c) == FPL_OK)
+                for (int k = 0; k < 4; k++) t[k] += c[k];
+        }
+        cerr << "FASTQ comments: " << t[0] << " records, " << t[1] << " fields, " << t[2] << " bytes, " << t[3] << " fields left out (control bytes)" << endl;
+    }
     if (in.textMode)
         cerr << "device parse: " << p.nTextBatches.load() << " chunks parsed on the device, " << p.nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;

@@ -27,6 +27,7 @@ static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
     InputFacts in;
     in.bam = !opt.from_stdin && fplh::is_bam_file(opt.in);
     if (opt.keepTags && !in.bam) error_exit("--keep_tags needs BAM input (--in " + opt.in + " is not a BAM file)");
+    if (opt.commentTags && !in.bam) error_exit("--comment_tags needs BAM input (--in " + opt.in + " is not a BAM file)");
     if (in.bam) {
         const DeviceApi::BamDecodeFn bamDecode = api.decode_bam;
         if (!api.process_bam_async || !bamDecode)
@@ -235,7 +236,7 @@ static InputPlan plan_input(const Options& opt, const InputFacts& in, const Devi
         p.bamReader = new fplh::BamReader(opt.in);
         if (!p.bamReader->ok()) error_exit("Failed to open file: " + opt.in);
         if (in.inflater) p.bamReader->set_inflater(api.inflate_bgzf, in.inflater);
-        p.bamReader->set_check_tags(opt.keepTags);
+        p.bamReader->set_check_tags(opt.keepTags || opt.commentTags);
     } else if (!p.chunked) {
         p.reader = new fplh::FastqReader(opt.in);
         if (!p.reader->ok()) error_exit("Failed to open file: " + opt.in);

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "fastplong_amd.h"
+#include "bam_comments.h"
 #include "fasta.h"
 
 using namespace std;
@@ -81,7 +82,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""}, {"comment_tags", 0, true, ""},
 };
 
 struct Args {
@@ -173,6 +174,9 @@ struct Options {
     bool bgzf = false; /* --bgzf: every .gz this run writes is BGZF blocks plus the EOF block */
     bool keepMods = false; /* --keep_mods: with --keep_tags, a trimmed or split record's MM / ML / MN are re-indexed, not dropped (csrc/bam_mod_rules.h) */
     bool keepTags = false; /* --keep_tags: BAM input's auxiliary fields and @RG lines go into the .bam outputs (README "BAM output") */
+    /* --comment_tags LIST: BAM input's auxiliary fields go behind the name lines of every FASTQ output (README "Tags as FASTQ comments") */
+    bool commentTags = false;
+    fplh::BamCommentSelection commentSel = {};
     string command; /* src/main.cpp:252-256 */
     time_t t1 = 0;
 };
@@ -336,6 +340,13 @@ static Options parse_options(int argc, char** argv) {
     if (p.keepTags && !bamOut) error_exit("--keep_tags needs an output whose name ends in .bam (--out or --failed_out)");
     p.keepMods = cmd.exist("keep_mods");
     if (p.keepMods && !p.keepTags) error_exit("--keep_mods needs --keep_tags");
+    p.commentTags = cmd.exist("comment_tags");
+    if (p.commentTags) {
+        if (!fplh::parse_comment_tags(cmd.str("comment_tags"), p.commentSel))
+            error_exit("--comment_tags takes * or a list of 1 to 32 two-character tags such as MM,ML (got: " + cmd.str("comment_tags") + ")");
+        const bool fastqOut = p.toStdout || (!p.out.empty() && !ends_with_bam(p.out)) || (!p.splitEnabled && !p.failedOut.empty() && !ends_with_bam(p.failedOut));
+        if (!fastqOut) error_exit("--comment_tags needs a FASTQ output (--out, --failed_out, --stdout or the --split files; a .bam output follows --keep_tags)");
+    }
     if (p.splitEnabled && ends_with_bam(p.out)) error_exit("--split / --split_by_lines do not write BAM files (--out " + p.out + ")");
 
     stringstream ss; /* src/main.cpp:252-256 */

@@ -5,6 +5,7 @@
 #ifndef FPLH_CLI_OUTPUT_H
 #define FPLH_CLI_OUTPUT_H
 
+#include "bam_comments.h"
 #include "bam_out.h"
 #include "bam_tags.h"
 #include "cli_options.h"
@@ -108,16 +109,26 @@ struct OutFile {
 static std::atomic<uint64_t> g_bamTagStats[4];
 /* --keep_mods: the same for its four counts */
 static std::atomic<uint64_t> g_bamModStats[4];
+/* --comment_tags: what the host's form counted (bam_comments.h) */
+static std::atomic<uint64_t> g_bamCommentStats[4];
 
 struct Outputs {
     OutFile fout, ffail;
     bool keepTags = false; /* --keep_tags: a .bam output's records carry their input record's auxiliary fields */
     bool keepMods = false; /* --keep_mods: ... with MM / ML / MN re-indexed where the record is trimmed or split */
+    const fplh::BamCommentSelection* comments = nullptr; /* --comment_tags: the FASTQ outputs' name lines carry the selected fields */
     int gzLevel = 4;
     bool bgzf = false; /* --bgzf: the pieces are framed by bgzf_into */
     fplh::SplitOutput* split = nullptr; /* --split / --split_by_lines: the workers' private writers take the passing reads */
     bool gatherOut = false;             /* --out is written as gather lists over the batches' own arrays (build_gather) */
 
+    /* --comment_tags: the fields behind the name lines of a batch's formatted pieces, in front of the deflate (src: bam_tag_sources
+       with mods on, over all pieces) */
+    void comment_pieces(vector<string>& pieces, const vector<fplh::BamTagSrc>& src) const {
+        uint64_t st[4] = {0, 0, 0, 0};
+        fplh::pieces_add_tag_comments(pieces, src, *comments, st);
+        for (int k = 0; k < 4; k++) g_bamCommentStats[k] += st[k];
+    }
     bool any_gz() const { return (fout && fout.gz) || (ffail && ffail.gz); }
     /* the pieces as `file` takes them (in parallel; pieces stay below 4 GiB: one slice of a batch) */
     /* tags: --keep_tags, the sources of the records of ALL pieces together, in their order (bam_tags.h) */
@@ -157,6 +168,7 @@ static Outputs open_outputs(const Options& opt, const string& bamReadGroups = st
     o.gzLevel = min(9, max(1, opt.compression));
     o.keepTags = opt.keepTags;
     o.keepMods = opt.keepMods;
+    o.comments = opt.commentTags ? &opt.commentSel : nullptr;
     o.fout.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     o.ffail.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     if (opt.splitEnabled)
@@ -166,7 +178,8 @@ static Outputs open_outputs(const Options& opt, const string& bamReadGroups = st
        one writer thread's copy into the page cache is the bottleneck either way (18 GB: 2.9 s from formatted pieces, 3.6 s
        from eight small entries per read), so files keep the pieces the formatter threads put together side by side.
        FPLH_NO_GATHER / FPLH_GATHER_FILES: measurement hooks */
-    o.gatherOut = o.fout && !o.fout.gz && !o.ffail && !opt.fragmentMode && !o.split && !getenv("FPLH_NO_GATHER");
+    /* (--comment_tags: the comments go into formatted text) */
+    o.gatherOut = o.fout && !o.fout.gz && !o.ffail && !opt.fragmentMode && !o.split && !o.comments && !getenv("FPLH_NO_GATHER");
     if (o.gatherOut && !getenv("FPLH_GATHER_FILES")) {
         struct stat ost;
         if (fstat(fileno(o.fout.f), &ost) == 0 && S_ISREG(ost.st_mode)) o.gatherOut = false;

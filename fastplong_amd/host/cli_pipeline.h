@@ -307,6 +307,16 @@ void Pipeline::enable_device_gzip() {
        batch" -- and with --device_gzip asked for: whether this form beats the host's deflate beside the BGZF inflate on the
        same CPUs has not been measured, so a BAM run keeps the host's path unless told otherwise.  Without --failed_out the
        decoded arrays are not even copied back (seq_out / qual_out NULL): the host formats nothing of such a batch. */
+    /* --comment_tags: the device's FASTQ form of a BAM-backed batch needs fpl_set_bam_comments besides; against a library without
+       it, or where a context refuses the list, the host formats every batch, without a word */
+    if (eligible && facts.bam && opt.deviceGzip && opt.commentTags && !bamOut) {
+        bool on = api.set_bam_comments != nullptr;
+        for (size_t d = 0; on && d < ctxs.size(); d++)
+            on = api.set_bam_comments(ctxs[d], (const char*)opt.commentSel.tag, opt.commentSel.n) == FPL_OK;
+        if (!on)
+            for (size_t d = 0; api.set_bam_comments && d < ctxs.size(); d++) (void)api.set_bam_comments(ctxs[d], nullptr, 0);
+        eligible = on;
+    }
     if (eligible && facts.bam && opt.deviceGzip) devBamGz = enable_on_all(api.set_bam_gzip, api.wait_bam_gz != nullptr, ctxs);
     bamKeepArrays = !devBamGz || out.ffail; /* (--failed_out is formatted on the host: it needs the decoded bases) */
     devBgzf = devBgzf && (devGz || devBamGz);
@@ -708,6 +718,11 @@ void Pipeline::format_stage(int f) {
             const bool tagOut = out.keepTags && out.fout && out.fout.bam && !w->dev_gz, tagFailed = out.keepTags && toFailed && out.ffail.bam;
             if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, out.keepMods);
             if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, out.keepMods);
+            /* --comment_tags: the same lists, with re-indexing on, for the outputs that are FASTQ text; in front of the deflate */
+            const bool noteOut = out.comments && w->batch.bam_backed && out.fout && !out.fout.bam && !w->dev_gz;
+            const bool noteFailed = out.comments && w->batch.bam_backed && toFailed && !out.ffail.bam;
+            if (noteOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, true), out.comment_pieces(w->outs, w->outTags);
+            if (noteFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, true), out.comment_pieces(w->faileds, w->failedTags);
             if (w->dev_gz) { /* (formatted for --failed_out alone) */
                 w->outs.resize(1);
                 w->outs[0].swap(w->gz_member);
@@ -821,8 +836,10 @@ void Pipeline::split_reads(Work* wp) { /* before note_reads: readBase is the ind
     for (int wk = 0; wk < workers; wk++) {
         if (plan[(size_t)wk].empty()) continue;
         auto job = [this, split, wp, wk, fl, ranges = std::move(plan[(size_t)wk])]() {
-            const bool gather = !fl && !split->gzipped();
+            const bool notes = out.comments && wp->batch.bam_backed; /* --comment_tags: the comments go into formatted text */
+            const bool gather = !fl && !split->gzipped() && !notes;
             vector<struct iovec> iov;
+            vector<fplh::BamTagSrc> src;
             string text;
             for (const PackRange& r : ranges) {
                 if (gather) { /* the worker's getWriter1()->writeString(outstr), as a gather list over the batch's arrays */
@@ -831,6 +848,13 @@ void Pipeline::split_reads(Work* wp) { /* before note_reads: readBase is the ind
                 } else {
                     text.clear();
                     fplh::format_range(wp->batch, wp->res.data(), r.first, r.last, text, nullptr, fl);
+                    if (notes) {
+                        uint64_t st[4] = {0, 0, 0, 0};
+                        src.clear();
+                        fplh::bam_tag_sources(wp->batch, wp->res.data(), r.first, r.last, fl, false, src, true);
+                        fplh::add_tag_comments(text, src.data(), src.size(), *out.comments, st);
+                        for (int k = 0; k < 4; k++) g_bamCommentStats[k] += st[k];
+                    }
                     split->write(wk, text);
                 }
                 if (r.mark >= 0) split->mark(wk, r.mark);

@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "bam.h"
+#include "bam_comments.h"
 #include "bam_out.h"
 #include "bam_tags.h"
 #include "../csrc/bam_out_rules.h"
@@ -129,6 +130,44 @@ int bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, cons
         for (int k = 0; k < 8; k++) mod_stats[k] = 0;
     fplh::pieces_to_bam_records(o, so, stats, mod_stats);
     fplh::pieces_to_bam_records(f, sf, stats + 4, mod_stats ? mod_stats + 4 : nullptr);
+    std::string oo, ff;
+    for (auto& x : o) oo += x;
+    for (auto& x : f) ff += x;
+    hand_out(oo, out, out_len);
+    hand_out(ff, failed, failed_len);
+    return 0;
+}
+/* --comment_tags as the CLI runs it on the host: the same batch, formatted in `threads` pieces, the sources derived with mods on,
+   the comments added (pieces_add_tag_comments).  out / failed: the text of --out / --failed_out; stats: four counts each.  -1: as
+   above, -2: the selection is not one (fpl::bamcomment::make_selection) */
+int bam_comment_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n, const fpl_fragment* frags,
+                     uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, const char* tags, int n_tags, char** out,
+                     uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats) {
+    fplh::BamCommentSelection sel;
+    if (!fpl::bamcomment::make_selection(tags, n_tags, sel)) return -2;
+    fplh::BamReader rd(path);
+    if (!rd.ok()) return -1;
+    Batch b;
+    if (rd.fill(b, ~0ull, 0x3FFFFFFFu) != n || !rd.error().empty() || b.n() != n) return -1;
+    if (b.seq.size()) {
+        memcpy(b.seq.data(), seq, b.seq.size());
+        memcpy(b.qual.data(), qual, b.seq.size());
+    }
+    fplh::FragmentList fl;
+    const bool fragments = n_frags != ~0u;
+    if (fragments) {
+        fl.frags.assign(frags, frags + n_frags);
+        fl.regs.assign(regs, regs + n_regs);
+        fl.index(n);
+    }
+    std::vector<std::string> o, f;
+    fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
+    std::vector<fplh::BamTagSrc> so, sf;
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so, true);
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf, true);
+    for (int k = 0; k < 8; k++) stats[k] = 0;
+    fplh::pieces_add_tag_comments(o, so, sel, stats);
+    fplh::pieces_add_tag_comments(f, sf, sel, stats + 4);
     std::string oo, ff;
     for (auto& x : o) oo += x;
     for (auto& x : f) ff += x;
@@ -305,6 +344,32 @@ int fplh_bam_mod_form(const char* path, const uint8_t* seq, const uint8_t* qual,
                       const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
                       uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats, uint64_t* mod_stats) {
     return bam_tag_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, out, out_len, failed, failed_len, stats, true, mod_stats);
+}
+/* test hooks of --comment_tags.  _form: the host form as the CLI runs it (bam_comment_form above; tags: 2 * n_tags bytes, n_tags -1:
+   every field); _text: the rule's text of the tag bytes p[0, len) under a selection, and its three counts (fields, bytes, left
+   out); _list: the CLI's reading of a LIST -> its number of tags (-1: every field), -2: malformed */
+int fplh_bam_comment_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n,
+                          const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, const char* tags,
+                          int n_tags, char** out, uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats) {
+    return bam_comment_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, tags, n_tags, out, out_len, failed, failed_len, stats);
+}
+int fplh_bam_comment_text(const uint8_t* p, uint64_t len, const char* tags, int n_tags, char** out, uint64_t* out_len, uint64_t* counts) {
+    fplh::BamCommentSelection sel;
+    if (!fpl::bamcomment::make_selection(tags, n_tags, sel)) return -2;
+    struct Sink {
+        std::string s;
+        void put(const char* q, uint32_t n) { s.append(q, n); }
+        void copy(const uint8_t* q, uint64_t n) { s.append((const char*)q, (size_t)n); }
+        uint64_t size() const { return s.size(); }
+    } sink;
+    const fpl::bamcomment::Counts c = fpl::bamcomment::comment_text(p, len, sel, fpl::bamtag::ByteScan(), sink);
+    counts[0] = c.fields, counts[1] = c.bytes, counts[2] = c.left_out;
+    hand_out(sink.s, out, out_len);
+    return 0;
+}
+int fplh_comment_tag_list(const char* list) {
+    fplh::BamCommentSelection sel;
+    return fplh::parse_comment_tags(list ? list : "", sel) ? sel.n : -2;
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */

@@ -527,6 +527,32 @@ int fpl_set_bam_mods(fpl_ctx* ctx, int on);
 int fpl_get_bam_mod_stats(fpl_ctx* ctx, uint64_t* out);
 
 /*
+ * The auxiliary fields of a BAM input's records as COMMENTS behind the names of a gzip batch's FASTQ text (README "Tags as FASTQ
+ * comments", --comment_tags; the rule and its wording: csrc/bam_comment_rules.h).  FPL_ABI_VERSION stays 10: both calls are found
+ * by symbol lookup; a caller of a library without them formats such batches on the host.
+ *
+ *   fpl_set_bam_comments   per context; tags holds 2 * n_tags bytes, the selection: n_tags 0 switches the comments off, -1 selects
+ *                      every field, 1 to 32 the fields whose two tag bytes equal one of the list's exactly.  More than 32 tags, or
+ *                      a byte outside [A-Za-z][A-Za-z0-9], is FPL_ERR_ARG and changes nothing.  It takes effect with the NEXT
+ *                      submission, like fpl_set_bam_tags, and changes the bytes of a gzip batch only where the batch holds BAM
+ *                      records (fpl_process_bam_async, fpl_process_bgzf_bam_async with fpl_set_bam_gzip on) AND its bytes are FASTQ
+ *                      text (FPL_GZIP_FASTQ), in member and in BGZF framing; every other batch ignores it.  It does not depend on
+ *                      fpl_set_bam_tags / fpl_set_bam_mods, which keep applying to FPL_GZIP_BAM only.  Then the name line of an
+ *                      output read ends with the selected ones among the fields its BAM record would carry with both of those
+ *                      switches on -- the parsed prefix for an unchanged record, the non-positional fields for a changed one, MM /
+ *                      ML / MN re-indexed for a changed record of a re-indexable input record --, in their order, each behind one
+ *                      tab, in the SAM text form: XX:A:c, XX:i:<decimal> for c C s S i I, XX:f:<what printf("%g") gives>, XX:Z: and
+ *                      XX:H: with the value, XX:B:<subtype> and ,<value> per element.  A selected A, Z or H field with a byte below
+ *                      0x20 or the byte 0x7F in its value is left out.  The deflate blocks are cut by the same rule; a batch is at
+ *                      most ten times its input record bytes longer than without the switch (a field's text is at most five times
+ *                      its bytes, and both fragments of a split read carry the read's fields).
+ *   fpl_get_bam_comment_stats   out[4], since the context was made: output records that got at least one field, fields written,
+ *                      comment bytes (tabs included), fields left out for control bytes.  It waits like fpl_get_bam_tag_stats.
+ */
+int fpl_set_bam_comments(fpl_ctx* ctx, const char* tags, int n_tags);
+int fpl_get_bam_comment_stats(fpl_ctx* ctx, uint64_t* out);
+
+/*
  * The BGZF blocks of a BAM inflated on the device (csrc/bgzf_inflate.h).  FPL_ABI_VERSION stays 10: a caller finds these three
  * calls by symbol lookup (dlsym), as it does the calls of v9 and v10, and a library without them is a valid v10 library -- the
  * caller then inflates on the host.

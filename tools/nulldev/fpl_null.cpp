@@ -314,6 +314,16 @@ int fpl_get_bam_mod_stats(fpl_ctx* ctx, uint64_t* out) {
     for (int k = 0; k < 4; k++) out[k] = 0;
     return FPL_OK;
 }
+/* (nor writes comments: the host formats every batch of a --comment_tags run) */
+int fpl_set_bam_comments(fpl_ctx* ctx, const char*, int n_tags) {
+    if (!ctx) return FPL_ERR_ARG;
+    return n_tags ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
+int fpl_get_bam_comment_stats(fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    return FPL_OK;
+}
 /* (BGZF inflate: no device, so no inflater -- a host that finds the calls gets no handle and inflates itself) */
 fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
 int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
