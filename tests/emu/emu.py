@@ -29,11 +29,15 @@ def use_trim_stats(on):
     _libs["want"] = LIB_TRIM_STATS if on else LIB
 
 
-def trim_stats():
-    """-> (groups of 64 reads k_trim_ends_batched took, reads it handed to its wave-per-read fallback) since the last call"""
-    out = (C.c_ulonglong * 2)()
+TRIM_STATS = ("groups", "p1b", "p2", "p3_wants", "p3_may", "p6", "p7_wants", "p7_may", "searches", "rounds")
+
+
+def trim_stats(full=False):
+    """-> (groups of 64 reads k_trim_ends_batched took, reads it handed to its wave-per-read fallback) since the last call; full: all
+    ten counters, in the order of TRIM_STATS (emu_trim_stats in emu_driver.cpp says what each counts)"""
+    out = (C.c_ulonglong * 10)()
     assert lib().emu_trim_stats(out) == 0, "a counter is no multiple of 64 lanes"
-    return int(out[0]), int(out[1])
+    return tuple(int(v) for v in out) if full else (int(out[0]), int(out[1]))
 
 
 def lib():

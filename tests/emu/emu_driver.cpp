@@ -137,13 +137,18 @@ extern "C" int emu_process_batch(const fpl_options* opt, const char* start, int 
 }
 
 #ifdef FPL_EMU_TRIM_STATS
-/* which path the end trims took, for tests/test_cut_emu.py (the build with the counters is a library of its own): out[0] = the groups
-   of 64 reads k_trim_ends_batched took, out[1] = the reads it handed to its wave-per-read fallback (P1b), counted since the last
-   call.  Every lane of a wave counts, so both are kept as multiples of 64 and divided here */
+/* which path the end trims took, for tests/test_cut_emu.py and tests/test_partial_emu.py (the build with the counters is a library of
+   its own), counted since the last call: out[0] = the groups of 64 reads k_trim_ends_batched took, out[1] = the reads it handed to its
+   wave-per-read fallback (P1b), out[2] = the candidates of the start window scan it confirmed (P2), out[3] / out[4] = the reads that
+   asked for a partial-pattern search at the start (P3) / that a lane handed to the wave search, out[5] .. out[7] = the same three at
+   the end (P6, P7), out[8] = the lane-parallel partial searches (one per group and end in which a lane had a candidate column),
+   out[9] = their rounds.  Every lane of a wave counts, so all ten are kept as multiples of 64 and divided here */
 extern "C" int emu_trim_stats(unsigned long long* out) {
-    const int whole = fpl::g_trim_stats[0] % 64 == 0 && fpl::g_trim_stats[1] % 64 == 0;
-    out[0] = fpl::g_trim_stats[0] / 64;
-    out[1] = fpl::g_trim_stats[1] / 64;
+    int whole = 1;
+    for (int i = 0; i < 10; i++) {
+        whole = whole && fpl::g_trim_stats[i] % 64 == 0;
+        out[i] = fpl::g_trim_stats[i] / 64;
+    }
     for (auto& v : fpl::g_trim_stats) v = 0;
     return whole ? 0 : -1;
 }

@@ -1,4 +1,4 @@
-"""The copy-edit-run runner that tools/scan_mutants.py, tools/stats_mutants.py and tools/cut_mutants.py share.  CPU only, not part of the test run.
+"""The copy-edit-run runner that tools/scan_mutants.py, tools/stats_mutants.py, tools/cut_mutants.py and tools/partial_mutants.py share.  CPU only, not part of the test run.
 
 A mutant is (name, what it does, [(file, search text, replacement, number of sites)]).  run_mutant copies the tree's sources to a
 temporary directory, applies the edits there (each search text must occur in its file exactly as often as the entry says: a stale
