@@ -54,10 +54,19 @@ constexpr u32 BAMMOD_KEPT_SHIFT = 4;
 /* the counters of a context: four of fpl_get_bam_mod_stats, then the candidates of the batch in flight (zeroed per batch) */
 constexpr u32 BAMMOD_COUNTERS = 5;
 
-__global__ void __launch_bounds__(256)
-k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __restrict__ rec_start, const fpl_read_result* __restrict__ res, u32 n_rec,
-                u32 fragment_mode, BamTagInfo* __restrict__ info, unsigned long long* __restrict__ counters, BamModInfo* __restrict__ minfo,
-                u32* __restrict__ cand, unsigned long long* __restrict__ mod_counters) {
+/* what a sibling of k_bam_tags_mods notes in the same walk (csrc/bam_moves.h): here, nothing */
+struct BamWalkNoMore {
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void field(const u8*, uint64_t, uint64_t, bool, bool) {}
+    __device__ __forceinline__ void end(u32, bool, u32) {}
+};
+/* the walk of k_bam_tags_mods.  more: begin() per record, field(p, at, n, positional, mod) per field of its prefix, end(i, a passing
+   fragment is changed, n_rec).  minfo == nullptr (a sibling's run without fpl_set_bam_mods): the modification fields are not noted */
+template <class More>
+__device__ __forceinline__ void bam_tags_mods_body(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __restrict__ rec_start,
+                                                   const fpl_read_result* __restrict__ res, u32 n_rec, u32 fragment_mode, BamTagInfo* __restrict__ info,
+                                                   unsigned long long* __restrict__ counters, BamModInfo* __restrict__ minfo, u32* __restrict__ cand,
+                                                   unsigned long long* __restrict__ mod_counters, More more) {
     unsigned long long c[4] = {0, 0, 0, 0};
     for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
         const u64 rs = rec_start[i];
@@ -73,6 +82,7 @@ k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __res
         bamtag::Walk w = {0, 0, false, false};
         bammod::Found fd = bammod::nothing_found();
         bool other = false;
+        more.begin();
         while (w.prefix < len) {
             const uint64_t n = bamtag::field_len(p + w.prefix, len - w.prefix, BamTagScan8());
             if (!n) break;
@@ -81,6 +91,7 @@ k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __res
             if (bamtag::positional(f)) w.positional = true, other = other || !mod;
             else w.kept += n;
             bammod::note(fd, p, w.prefix, n);
+            more.field(p, w.prefix, n, bamtag::positional(f), mod);
             w.prefix += n;
         }
         w.whole = w.prefix == len;
@@ -101,6 +112,8 @@ k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __res
                 c[3] += w.whole ? 0 : 1;
             }
         info[i] = t;
+        more.end(i, any_changed, n_rec);
+        if (!minfo) continue;
         BamModInfo m;
         m.mm_at = (u32)fd.mm_at, m.mm_len = (u32)fd.mm_len, m.ml_at = (u32)fd.ml_at, m.ml_len = (u32)fd.ml_len, m.mn_at = (u32)fd.mn_at, m.mn_len = (u32)fd.mn_len;
         m.counts = (fd.n_mm < 255u ? fd.n_mm : 255u) | (fd.n_ml < 255u ? fd.n_ml : 255u) << 8 | (fd.n_mn < 255u ? fd.n_mn : 255u) << 16 | (other ? 1u << 24 : 0u);
@@ -119,6 +132,12 @@ k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __res
         for (int d = 1; d < 64; d <<= 1) v += shfl_xor_u64(v, d);
         if (lane_id() == 0 && v) atomicAdd(&counters[k], (unsigned long long)v);
     }
+}
+__global__ void __launch_bounds__(256)
+k_bam_tags_mods(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __restrict__ rec_start, const fpl_read_result* __restrict__ res, u32 n_rec,
+                u32 fragment_mode, BamTagInfo* __restrict__ info, unsigned long long* __restrict__ counters, BamModInfo* __restrict__ minfo,
+                u32* __restrict__ cand, unsigned long long* __restrict__ mod_counters) {
+    bam_tags_mods_body(bam, buf_bytes, rec_start, res, n_rec, fragment_mode, info, counters, minfo, cand, mod_counters, BamWalkNoMore{});
 }
 
 /* nibbles of the word (4 packed bytes, 8 bases) equal to code: bit 4 k of the result for nibble k */
@@ -351,6 +370,81 @@ k_bam_mods_plan(const u8* __restrict__ bam, u64 buf_bytes, const uint64_t* __res
     }
 }
 
+/* where a tail that writes a fragment's fields one by one stands: d runs to end, the fragment's last tag byte */
+struct BamTailOut {
+    u8* d;
+    u8* end;
+    /* len bytes of src, never past the fragment's end (never: the lengths are the plan kernels') */
+    __device__ __forceinline__ void put(const u8* src, u32 len) {
+        if (len > (u32)(end - d)) len = (u32)(end - d);
+        gz_wave_copy(d, src, len);
+        d += len;
+    }
+};
+/* the field of len bytes at p + o of a fragment whose modification fields are re-indexed: one of the three is written from the plan
+   (true), any other is left to the caller */
+__device__ __forceinline__ bool bammod_put_field(BamTailOut& w, const u8* p, u32 o, u32 len, const BamModInfo& m, const BamModPlan* plan, int f, u32 fl) {
+    const u32 lane = (u32)lane_id();
+    const bool has_mn = (m.counts >> 16 & 255u) != 0;
+    if (o == m.mm_at) {
+        const u8* v = p + o + 3;
+        w.put(p + o, 3);
+        for (u32 g = 0; g < plan->n_groups && g < bammod::MAX_GROUPS; g++) {
+            w.put(v + plan->hdr_at[g], plan->hdr_len[g]);
+            const BamModCut c = plan->cut[f][g];
+            if (c.first != BAMMOD_NONE) {
+                const u32 nd = bammod::digits_of(c.first);
+                u8 head[16]; /* ',' and the digits */
+                head[0] = (u8)',';
+                u32 x = c.first;
+                for (u32 k = nd; k >= 1; k--) head[k] = (u8)('0' + x % 10u), x /= 10u;
+                const u32 hn = nd + 1 > (u32)(w.end - w.d) ? (u32)(w.end - w.d) : nd + 1;
+                if (lane < hn) w.d[lane] = head[lane];
+                w.d += hn;
+                w.put(v + c.rest_at, c.rest_len);
+            }
+            const u8 semi = (u8)';';
+            if (w.d < w.end) {
+                if (lane == 0) w.d[0] = semi;
+                w.d++;
+            }
+        }
+        if (w.d < w.end) {
+            if (lane == 0) w.d[0] = 0;
+            w.d++;
+        }
+        return true;
+    }
+    if (o == m.ml_at) {
+        w.put(p + o, 4);
+        if (w.end - w.d >= 4) {
+            if (lane < 4) w.d[lane] = (u8)(plan->ml_count[f] >> (8u * lane));
+            w.d += 4;
+        }
+        for (u32 g = 0; g < plan->n_groups && g < bammod::MAX_GROUPS; g++) {
+            const BamModCut c = plan->cut[f][g];
+            if (c.first != BAMMOD_NONE) w.put(p + o + 8 + c.ml_at, c.ml_len);
+        }
+        return true;
+    }
+    if (has_mn && o == m.mn_at) {
+        w.put(p + o, 3);
+        const u32 nv = len - 3 > (u32)(w.end - w.d) ? (u32)(w.end - w.d) : len - 3;
+        if (lane < nv) w.d[lane] = (u8)(lane < 4 ? fl >> (8u * lane) : 0u);
+        w.d += nv;
+        return true;
+    }
+    return false;
+}
+/* the bytes of the next field of the prefix, at p + o: lane 0 walks */
+__device__ __forceinline__ u32 bam_tail_field_len(const u8* p, u32 o, u32 prefix) {
+    u32 len = 0;
+    if (lane_id() == 0) {
+        len = (u32)bamtag::field_len(p + o, prefix - o, BamTagScan8());
+        if (!len) len = prefix - o; /* (every field of the prefix parses: the walk kernel went over it by the same rule) */
+    }
+    return shfl_u32(len, 0);
+}
 /* BamTagTail, and for a re-indexed fragment the fields one by one */
 struct BamModTail {
     BamTagTail tags;
@@ -365,68 +459,13 @@ struct BamModTail {
         const BamModInfo m = minfo[i];
         const BamModPlan* plan = plans + m.slot;
         if (lane < 4) rec[lane] = (u8)((bamout::fixed_word(0, nl, fl) + n) >> (8u * lane));
-        u8* const end = d + n;
-        /* len bytes of src, never past the fragment's end (never: the lengths are k_bam_mods_plan's) */
-        auto put = [&](const u8* src, u32 len) {
-            if (len > (u32)(end - d)) len = (u32)(end - d);
-            gz_wave_copy(d, src, len);
-            d += len;
-        };
-        const bool has_mn = (m.counts >> 16 & 255u) != 0;
-        for (u32 o = 0; o < t.prefix && d < end;) { /* wave-uniform */
-            u32 len = 0;
-            if (lane == 0) {
-                len = (u32)bamtag::field_len(p + o, t.prefix - o, BamTagScan8());
-                if (!len) len = t.prefix - o; /* (every field of the prefix parses: k_bam_tags_mods walked it by the same rule) */
-            }
-            len = shfl_u32(len, 0);
-            if (o == m.mm_at) {
-                const u8* v = p + o + 3;
-                put(p + o, 3);
-                for (u32 g = 0; g < plan->n_groups && g < bammod::MAX_GROUPS; g++) {
-                    put(v + plan->hdr_at[g], plan->hdr_len[g]);
-                    const BamModCut c = plan->cut[f][g];
-                    if (c.first != BAMMOD_NONE) {
-                        const u32 nd = bammod::digits_of(c.first);
-                        u8 head[16]; /* ',' and the digits */
-                        head[0] = (u8)',';
-                        u32 x = c.first;
-                        for (u32 k = nd; k >= 1; k--) head[k] = (u8)('0' + x % 10u), x /= 10u;
-                        const u32 hn = nd + 1 > (u32)(end - d) ? (u32)(end - d) : nd + 1;
-                        if (lane < hn) d[lane] = head[lane];
-                        d += hn;
-                        put(v + c.rest_at, c.rest_len);
-                    }
-                    const u8 semi = (u8)';';
-                    if (d < end) {
-                        if (lane == 0) d[0] = semi;
-                        d++;
-                    }
-                }
-                if (d < end) {
-                    if (lane == 0) d[0] = 0;
-                    d++;
-                }
-            } else if (o == m.ml_at) {
-                put(p + o, 4);
-                if (end - d >= 4) {
-                    if (lane < 4) d[lane] = (u8)(plan->ml_count[f] >> (8u * lane));
-                    d += 4;
-                }
-                for (u32 g = 0; g < plan->n_groups && g < bammod::MAX_GROUPS; g++) {
-                    const BamModCut c = plan->cut[f][g];
-                    if (c.first != BAMMOD_NONE) put(p + o + 8 + c.ml_at, c.ml_len);
-                }
-            } else if (has_mn && o == m.mn_at) {
-                put(p + o, 3);
-                const u32 nv = len - 3 > (u32)(end - d) ? (u32)(end - d) : len - 3;
-                if (lane < nv) d[lane] = (u8)(lane < 4 ? fl >> (8u * lane) : 0u);
-                d += nv;
-            } else if (!bamtag::positional(p + o))
-                put(p + o, len);
+        BamTailOut w = {d, d + n};
+        for (u32 o = 0; o < t.prefix && w.d < w.end;) { /* wave-uniform */
+            const u32 len = bam_tail_field_len(p, o, t.prefix);
+            if (!bammod_put_field(w, p, o, len, m, plan, f, fl) && !bamtag::positional(p + o)) w.put(p + o, len);
             o += len;
         }
-        return end;
+        return w.end;
     }
 };
 __global__ void __launch_bounds__(256)

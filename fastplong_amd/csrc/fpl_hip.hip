@@ -29,6 +29,7 @@
 #include "bam_emit.h"
 #include "bam_tags.h"
 #include "bam_mods.h"
+#include "bam_moves.h"
 #include "bam_comments.h"
 #include "bam_decode.h"
 #include "bgzf_inflate.h"
@@ -279,6 +280,18 @@ int fpl_get_bam_comment_stats(fpl_ctx* ctx, uint64_t* out) {
     FPL_HIP(hipStreamSynchronize(ctx->stream)); /* (k_bam_comment_len of every batch submitted so far has added its share) */
     unsigned long long c[4];
     FPL_HIP(hipMemcpy(c, ctx->d_note_counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; k++) out[k] = c[k];
+    return FPL_OK;
+}
+
+int fpl_get_bam_move_stats(fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    if (!ctx->d_move_counters.ptr) return FPL_OK; /* (no batch has re-indexed anything yet) */
+    FPL_HIP(hipSetDevice(ctx->device));
+    FPL_HIP(hipStreamSynchronize(ctx->stream)); /* (k_bam_moves_plan of every batch submitted so far has added its share) */
+    unsigned long long c[4];
+    FPL_HIP(hipMemcpy(c, ctx->d_move_counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; k++) out[k] = c[k];
     return FPL_OK;
 }

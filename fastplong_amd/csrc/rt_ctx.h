@@ -133,6 +133,10 @@ struct fpl_ctx {
             DevBuf<BamModInfo> d_mod_info; /* k_bam_tags_mods -> k_bam_mods_plan and the compose kernel: one per input record */
             DevBuf<u32> d_mod_cand;        /* the candidate records */
             DevBuf<BamModPlan> d_mod_plan; /* one per candidate (sized for every record: how many there are only the device knows) */
+            bool moves = false;   /* ... with mv and ts re-indexed (fpl_set_bam_moves; csrc/bam_moves.h) */
+            DevBuf<BamMoveInfo> d_move_info; /* k_bam_tags_moves -> k_bam_moves_plan and the compose kernel: one per input record */
+            DevBuf<u32> d_move_cand;         /* the candidate records */
+            DevBuf<BamMovePlan> d_move_plan; /* one per candidate, sized as d_mod_plan is */
             /* ... or FASTQ text whose name lines carry the input records' fields as comments (fpl_set_bam_comments;
                csrc/bam_comments.h): the selection when the batch was submitted (n 0: off) */
             bamcomment::Selection notes = {};
@@ -187,6 +191,8 @@ struct fpl_ctx {
     bamcomment::Selection bam_comments = {}; /* fpl_set_bam_comments: the same (n 0: off) */
     DevBuf<unsigned long long> d_note_counters; /* fpl_get_bam_comment_stats: four counts k_bam_comment_len adds to */
     DevBuf<unsigned long long> d_note_work;     /* what k_bam_tags_mods / k_bam_mods_plan count for such a batch: nobody reads it but they (zeroed per batch) */
+    bool bam_moves = false;    /* fpl_set_bam_moves: the same */
+    DevBuf<unsigned long long> d_move_counters; /* fpl_get_bam_move_stats: four counts, and the candidates of the batch in flight (csrc/bam_moves.h) */
     DevBuf<unsigned long long> d_mod_counters; /* fpl_get_bam_mod_stats: four counts, and the candidates of the batch in flight (csrc/bam_mods.h) */
     DevBuf<unsigned long long> d_tag_counters; /* fpl_get_bam_tag_stats: four counts k_bam_tags adds to (made with the first tagged batch) */
     /* fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async: the tail between two submissions and the walk's state live on the

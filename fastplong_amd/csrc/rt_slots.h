@@ -60,23 +60,48 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
             FPL_HIP(hipMemsetAsync(ctx->d_tag_counters.ptr, 0, 4 * sizeof(unsigned long long), st));
         }
         FPL_HIP(g.d_tag_info.grow(n, 4096 / sizeof(BamTagInfo)));
-        if (g.mods) { /* the same walk notes the MM / ML / MN fields; a wave per candidate record plans its fragments' fields */
-            if (!ctx->d_mod_counters.ptr) {
-                FPL_HIP(ctx->d_mod_counters.alloc(BAMMOD_COUNTERS));
-                FPL_HIP(hipMemsetAsync(ctx->d_mod_counters.ptr, 0, BAMMOD_COUNTERS * sizeof(unsigned long long), st));
+        if (g.mods || g.moves) { /* the same walk notes the MM / ML / MN fields, the mv and ts fields or both; a wave per candidate record plans its fragments' fields */
+            const dim3 lanes(std::max<u32>(1u, std::min<u32>((n + 255) / 256, 8u * ctx->n_cu))), waves(std::max<u32>(1u, std::min<u32>((n + 3) / 4, 8u * ctx->n_cu)));
+            const u32 fragment_mode = (u32)(ctx->hcfg.defer ? 1 : 0);
+            if (g.mods) {
+                if (!ctx->d_mod_counters.ptr) {
+                    FPL_HIP(ctx->d_mod_counters.alloc(BAMMOD_COUNTERS));
+                    FPL_HIP(hipMemsetAsync(ctx->d_mod_counters.ptr, 0, BAMMOD_COUNTERS * sizeof(unsigned long long), st));
+                }
+                FPL_HIP(g.d_mod_info.grow(n, 4096 / sizeof(BamModInfo)));
+                FPL_HIP(g.d_mod_cand.grow(n, 1024));
+                FPL_HIP(g.d_mod_plan.grow(n, 16));
+                FPL_HIP(hipMemsetAsync(ctx->d_mod_counters.ptr + 4, 0, sizeof(unsigned long long), st));
             }
-            FPL_HIP(g.d_mod_info.grow(n, 4096 / sizeof(BamModInfo)));
-            FPL_HIP(g.d_mod_cand.grow(n, 1024));
-            FPL_HIP(g.d_mod_plan.grow(n, 16));
-            FPL_HIP(hipMemsetAsync(ctx->d_mod_counters.ptr + 4, 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(k_bam_tags_mods, dim3(std::max<u32>(1u, std::min<u32>((n + 255) / 256, 8u * ctx->n_cu))), dim3(256), 0, st,
-                               (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
-                               (u32)(ctx->hcfg.defer ? 1 : 0), g.d_tag_info.ptr, ctx->d_tag_counters.ptr, g.d_mod_info.ptr, g.d_mod_cand.ptr,
-                               ctx->d_mod_counters.ptr);
-            hipLaunchKernelGGL(k_bam_mods_plan, dim3(std::max<u32>(1u, std::min<u32>((n + 3) / 4, 8u * ctx->n_cu))), dim3(256), 0, st,
-                               (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
-                               (u32)(ctx->hcfg.defer ? 1 : 0), g.d_tag_info.ptr, (const BamModInfo*)g.d_mod_info.ptr, (const u32*)g.d_mod_cand.ptr,
-                               g.d_mod_plan.ptr, ctx->d_tag_counters.ptr, ctx->d_mod_counters.ptr);
+            if (g.moves) {
+                if (!ctx->d_move_counters.ptr) {
+                    FPL_HIP(ctx->d_move_counters.alloc(BAMMOVE_COUNTERS));
+                    FPL_HIP(hipMemsetAsync(ctx->d_move_counters.ptr, 0, BAMMOVE_COUNTERS * sizeof(unsigned long long), st));
+                }
+                FPL_HIP(g.d_move_info.grow(n, 4096 / sizeof(BamMoveInfo)));
+                FPL_HIP(g.d_move_cand.grow(n, 1024));
+                FPL_HIP(g.d_move_plan.grow(n, 4096 / sizeof(BamMovePlan)));
+                FPL_HIP(hipMemsetAsync(ctx->d_move_counters.ptr + 4, 0, sizeof(unsigned long long), st));
+            }
+            /* (without fpl_set_bam_mods the buffers of its walk are nullptr: k_bam_tags_moves leaves them alone) */
+            BamModInfo* const minfo = g.mods ? g.d_mod_info.ptr : nullptr;
+            u32* const mcand = g.mods ? g.d_mod_cand.ptr : nullptr;
+            unsigned long long* const mcount = g.mods ? ctx->d_mod_counters.ptr : nullptr;
+            if (g.moves)
+                hipLaunchKernelGGL(k_bam_tags_moves, lanes, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                                   (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, ctx->d_tag_counters.ptr, minfo, mcand, mcount,
+                                   g.d_move_info.ptr, g.d_move_cand.ptr, ctx->d_move_counters.ptr);
+            else
+                hipLaunchKernelGGL(k_bam_tags_mods, lanes, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                                   (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, ctx->d_tag_counters.ptr, minfo, mcand, mcount);
+            if (g.mods)
+                hipLaunchKernelGGL(k_bam_mods_plan, waves, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                                   (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, (const BamModInfo*)g.d_mod_info.ptr,
+                                   (const u32*)g.d_mod_cand.ptr, g.d_mod_plan.ptr, ctx->d_tag_counters.ptr, ctx->d_mod_counters.ptr);
+            if (g.moves) /* (behind the other plan: it adds to the lengths that one wrote) */
+                hipLaunchKernelGGL(k_bam_moves_plan, waves, dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr,
+                                   (const fpl_read_result*)sl.d_results.ptr, n, fragment_mode, g.d_tag_info.ptr, (const BamMoveInfo*)g.d_move_info.ptr,
+                                   (const u32*)g.d_move_cand.ptr, g.d_move_plan.ptr, ctx->d_tag_counters.ptr, ctx->d_move_counters.ptr);
         } else {
             hipLaunchKernelGGL(k_bam_tags, dim3(std::max<u32>(1u, std::min<u32>((n + 255) / 256, 8u * ctx->n_cu))), dim3(256), 0, st,
                                (const u8*)sl.bam.d_bam.ptr, (u64)sl.bam.bytes, (const uint64_t*)sl.bam.d_rec.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
@@ -147,7 +172,14 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
     /* (g.records: the bytes are BAM records, csrc/bam_emit.h; the block kernels below do not care) */
-    if (g.tags && g.mods && g.records && bam_records(sl.kind))
+    if (g.tags && g.moves && g.records && bam_records(sl.kind))
+        hipLaunchKernelGGL(k_bamout_compose_bam_moves, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+                           (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr,
+                           (const BamModInfo*)(g.mods ? g.d_mod_info.ptr : nullptr), (const BamModPlan*)(g.mods ? g.d_mod_plan.ptr : nullptr),
+                           (const BamMoveInfo*)g.d_move_info.ptr, (const BamMovePlan*)g.d_move_plan.ptr, (const u64*)g.d_rec_off.ptr, g.d_comp.ptr,
+                           (u64)h.total);
+    else if (g.tags && g.mods && g.records && bam_records(sl.kind))
         hipLaunchKernelGGL(k_bamout_compose_bam_mods, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr, (const BamModInfo*)g.d_mod_info.ptr,
@@ -266,6 +298,7 @@ static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out
     sl.gzip.records = ctx->gzip_records;
     sl.gzip.tags = ctx->bam_tags;
     sl.gzip.mods = ctx->bam_tags && ctx->bam_mods;
+    sl.gzip.moves = ctx->bam_tags && ctx->bam_moves;
     sl.gzip.notes = ctx->bam_comments;
     sl.gzip.bgzf = ctx->gzip_bgzf || sl.gzip.records; /* BAM records are BGZF whatever the framing says (here and not in gz_layout: a staged kind's layout runs in its start call or its wait) */
     sl.n_reads = 0;

@@ -144,6 +144,12 @@ int fpl_set_bam_comments(fpl_ctx* ctx, const char* tags, int n_tags) {
     return FPL_OK;
 }
 
+int fpl_set_bam_moves(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    ctx->bam_moves = on != 0; /* (read by slot_begin; without fpl_set_bam_tags it changes nothing) */
+    return FPL_OK;
+}
+
 static int wait_text(fpl_ctx* ctx, fpl_text_result* out, const fpl_read_result** results, const uint32_t** line_starts,
                      const uint8_t** gz, uint64_t* gz_len) {
     if (!ctx || !out) return FPL_ERR_ARG;

@@ -27,6 +27,7 @@ EXPORTS = [
     "fpl_set_text_gzip", "fpl_wait_text_gz", "fpl_get_gzip_batches",
     "fpl_process_bam_async", "fpl_decode_bam", "fpl_set_bam_gzip", "fpl_wait_bam_gz", "fpl_set_gzip_framing", "fpl_set_gzip_records",
     "fpl_set_bam_tags", "fpl_get_bam_tag_stats", "fpl_set_bam_mods", "fpl_get_bam_mod_stats",
+    "fpl_set_bam_moves", "fpl_get_bam_move_stats",
     "fpl_set_bam_comments", "fpl_get_bam_comment_stats",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
     "fpl_emit_batch_device",
@@ -178,6 +179,11 @@ def load_library(path=None):
         L.fpl_set_bam_mods.argtypes = [C.c_void_p, C.c_int]
         L.fpl_get_bam_mod_stats.restype = C.c_int
         L.fpl_get_bam_mod_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "fpl_set_bam_moves"):  # (the same for Engine.set_bam_moves / bam_move_stats)
+        L.fpl_set_bam_moves.restype = C.c_int
+        L.fpl_set_bam_moves.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_get_bam_move_stats.restype = C.c_int
+        L.fpl_get_bam_move_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     if hasattr(L, "fpl_inflate_bgzf"):  # (found by name, the ABI version is still 10: without them Inflater raises)
         L.fpl_inflater_create.restype = C.c_void_p
         L.fpl_inflater_create.argtypes = [C.c_int32]
@@ -810,6 +816,23 @@ class Engine:
             raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_comment_stats")
         out = (C.c_uint64 * 4)()
         self._check(self.L.fpl_get_bam_comment_stats(self.h, out), "fpl_get_bam_comment_stats")
+        return tuple(int(v) for v in out)
+
+    def set_bam_moves(self, on):
+        """fpl_set_bam_moves: with set_bam_tags(True), the trimmed and split records of the batches submitted from now on get their
+        move table mv and its ts re-indexed for their piece of the read (README "BAM output", --keep_moves) in place of losing the
+        table; independent of set_bam_mods"""
+        if not hasattr(self.L, "fpl_set_bam_moves"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_bam_moves")
+        self._check(self.L.fpl_set_bam_moves(self.h, 1 if on else 0), "fpl_set_bam_moves")
+
+    def bam_move_stats(self):
+        """fpl_get_bam_move_stats -> (output records re-indexed, changed records whose move table was not re-indexable and was
+        dropped, table entries kept, entries cut away), since the engine was made"""
+        if not hasattr(self.L, "fpl_get_bam_move_stats"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_get_bam_move_stats")
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.fpl_get_bam_move_stats(self.h, out), "fpl_get_bam_move_stats")
         return tuple(int(v) for v in out)
 
     def gzip_batches(self):

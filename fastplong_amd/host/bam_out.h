@@ -9,6 +9,8 @@
  *
  * --keep_mods: a changed record of a re-indexable input record (csrc/bam_mod_rules.h) gets its MM / ML / MN fields rewritten for
  * its piece of the read in place of losing them.
+ *
+ * --keep_moves: the same for the move table mv and its ts (csrc/bam_move_rules.h); either switch decides its own fields.
  */
 #ifndef FPLH_BAM_OUT_H
 #define FPLH_BAM_OUT_H
@@ -40,18 +42,22 @@ struct BamTagSrc {
        fragment_mode: a --break / --mask run, in which no record is re-indexable */
     uint32_t start = 0, len = 0;
     bool mods = false, fragment_mode = false;
+    bool moves = false; /* --keep_moves (csrc/bam_move_rules.h): the switch is on */
     BamTagSrc(const uint8_t* r, bool c) : rec(r), changed(c) {}
-    BamTagSrc(const uint8_t* r, bool c, uint32_t s, uint32_t n, bool m, bool fm) : rec(r), changed(c), start(s), len(n), mods(m), fragment_mode(fm) {}
+    BamTagSrc(const uint8_t* r, bool c, uint32_t s, uint32_t n, bool m, bool fm, bool mv = false)
+        : rec(r), changed(c), start(s), len(n), mods(m), fragment_mode(fm), moves(mv) {}
 };
 /* the same with tags: record k of the text gets what the rule picks of src[k] (k >= n_src: nothing).  stats (4 counts, added to):
    records that kept every field of their parsed prefix, records that lost positional fields, tag bytes written, records whose
    region did not parse to its end.  mod_stats (4 counts, added to; only sources with `mods` move them): records re-indexed, changed
-   records whose modification fields were not re-indexable and went the old way, modification positions kept, positions cut away */
+   records whose modification fields were not re-indexable and went the old way, modification positions kept, positions cut away.
+   move_stats (the same for sources with `moves`): records re-indexed, changed records with a table that was not re-indexable, table
+   entries kept, entries cut away */
 void fastq_to_bam_records(const std::string& text, const BamTagSrc* src, size_t n_src, std::string& out, uint64_t* stats,
-                          uint64_t* mod_stats = nullptr);
+                          uint64_t* mod_stats = nullptr, uint64_t* move_stats = nullptr);
 /* what the rules pick of the input record of s (s.rec is not nullptr) -- the tag bytes of its output record --, appended to out
-   -> the bytes appended; stats, mod_stats: as above, nullptr for not wanted */
-uint64_t bam_record_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats);
+   -> the bytes appended; stats, mod_stats, move_stats: as above, nullptr for not wanted */
+uint64_t bam_record_tags(const BamTagSrc& s, std::string& out, uint64_t* stats, uint64_t* mod_stats, uint64_t* move_stats = nullptr);
 /* records of a formatted text: a quarter of its line ends */
 size_t fastq_record_count(const std::string& text);
 

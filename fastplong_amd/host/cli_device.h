@@ -46,6 +46,9 @@ struct DeviceApi {
     /* --keep_mods: ... and re-index MM / ML / MN in them (found by name; without them the host writes every record of such a run) */
     SetGzipFn set_bam_mods = nullptr;
     BamTagStatsFn get_bam_mod_stats = nullptr;
+    /* --keep_moves: ... and the move table and ts (found by name, and without them the host writes, in the same way) */
+    SetGzipFn set_bam_moves = nullptr;
+    BamTagStatsFn get_bam_move_stats = nullptr;
     /* --comment_tags: the device's FASTQ gzip form of a BAM-backed batch writes the fields behind the names (found by name; without
        it the host formats every batch of such a run) */
     typedef int (*SetBamCommentsFn)(fpl_ctx*, const char*, int);
@@ -71,6 +74,8 @@ static DeviceApi load_device_api() {
     a.get_bam_tag_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_tag_stats");
     a.set_bam_mods = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_mods");
     a.get_bam_mod_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_mod_stats");
+    a.set_bam_moves = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_moves");
+    a.get_bam_move_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_move_stats");
     a.set_bam_comments = (DeviceApi::SetBamCommentsFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_comments");
     a.get_bam_comment_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_comment_stats");
     return a;

@@ -56,6 +56,17 @@ static void print_pipeline_summary(const Pipeline& p) {
         cerr << "BAM modifications: " << t[0] << " records re-indexed, " << t[1] << " not re-indexable and dropped, " << t[2]
              << " positions kept, " << t[3] << " cut away" << endl;
     }
+    if (p.opt.keepMoves) { /* the same two forms */
+        uint64_t t[4];
+        for (int k = 0; k < 4; k++) t[k] = g_bamMoveStats[k].load();
+        for (fpl_ctx* ctx : p.ctxs) {
+            uint64_t c[4] = {0, 0, 0, 0};
+            if (p.api.get_bam_move_stats && p.api.get_bam_move_stats(ctx, c) == FPL_OK)
+                for (int k = 0; k < 4; k++) t[k] += c[k];
+        }
+        cerr << "BAM move tables: " << t[0] << " records re-indexed, " << t[1] << " not re-indexable and dropped, " << t[2]
+             << " entries kept, " << t[3] << " cut away" << endl;
+    }
     if (p.opt.commentTags) { /* the same two forms */
         uint64_t t[4];
         for (int k = 0; k < 4; k++) t[k] = g_bamCommentStats[k].load();

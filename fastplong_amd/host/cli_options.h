@@ -82,7 +82,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""}, {"comment_tags", 0, true, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""}, {"keep_moves", 0, false, ""}, {"comment_tags", 0, true, ""},
 };
 
 struct Args {
@@ -173,6 +173,7 @@ struct Options {
     bool gzStream = false, deviceParse = false, hostParse = false, hostGzip = false, deviceGzip = false, deviceInflate = false;
     bool bgzf = false; /* --bgzf: every .gz this run writes is BGZF blocks plus the EOF block */
     bool keepMods = false; /* --keep_mods: with --keep_tags, a trimmed or split record's MM / ML / MN are re-indexed, not dropped (csrc/bam_mod_rules.h) */
+    bool keepMoves = false; /* --keep_moves: with --keep_tags, a trimmed or split record's move table mv and its ts are re-indexed, not dropped (csrc/bam_move_rules.h) */
     bool keepTags = false; /* --keep_tags: BAM input's auxiliary fields and @RG lines go into the .bam outputs (README "BAM output") */
     /* --comment_tags LIST: BAM input's auxiliary fields go behind the name lines of every FASTQ output (README "Tags as FASTQ comments") */
     bool commentTags = false;
@@ -340,6 +341,8 @@ static Options parse_options(int argc, char** argv) {
     if (p.keepTags && !bamOut) error_exit("--keep_tags needs an output whose name ends in .bam (--out or --failed_out)");
     p.keepMods = cmd.exist("keep_mods");
     if (p.keepMods && !p.keepTags) error_exit("--keep_mods needs --keep_tags");
+    p.keepMoves = cmd.exist("keep_moves");
+    if (p.keepMoves && !p.keepTags) error_exit("--keep_moves needs --keep_tags");
     p.commentTags = cmd.exist("comment_tags");
     if (p.commentTags) {
         if (!fplh::parse_comment_tags(cmd.str("comment_tags"), p.commentSel))

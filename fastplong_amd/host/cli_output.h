@@ -109,6 +109,8 @@ struct OutFile {
 static std::atomic<uint64_t> g_bamTagStats[4];
 /* --keep_mods: the same for its four counts */
 static std::atomic<uint64_t> g_bamModStats[4];
+/* --keep_moves: the same */
+static std::atomic<uint64_t> g_bamMoveStats[4];
 /* --comment_tags: what the host's form counted (bam_comments.h) */
 static std::atomic<uint64_t> g_bamCommentStats[4];
 
@@ -116,6 +118,7 @@ struct Outputs {
     OutFile fout, ffail;
     bool keepTags = false; /* --keep_tags: a .bam output's records carry their input record's auxiliary fields */
     bool keepMods = false; /* --keep_mods: ... with MM / ML / MN re-indexed where the record is trimmed or split */
+    bool keepMoves = false; /* --keep_moves: ... with the move table and ts re-indexed in the same way */
     const fplh::BamCommentSelection* comments = nullptr; /* --comment_tags: the FASTQ outputs' name lines carry the selected fields */
     int gzLevel = 4;
     bool bgzf = false; /* --bgzf: the pieces are framed by bgzf_into */
@@ -136,9 +139,9 @@ struct Outputs {
         const int level = gzLevel;
         const bool blocks = file.bgzf, records = file.bam;
         if (records && tags) {
-            uint64_t st[4] = {0, 0, 0, 0}, ms[4] = {0, 0, 0, 0};
-            fplh::pieces_to_bam_records(pieces, *tags, st, ms);
-            for (int k = 0; k < 4; k++) g_bamTagStats[k] += st[k], g_bamModStats[k] += ms[k];
+            uint64_t st[4] = {0, 0, 0, 0}, ms[4] = {0, 0, 0, 0}, vs[4] = {0, 0, 0, 0};
+            fplh::pieces_to_bam_records(pieces, *tags, st, ms, vs);
+            for (int k = 0; k < 4; k++) g_bamTagStats[k] += st[k], g_bamModStats[k] += ms[k], g_bamMoveStats[k] += vs[k];
         }
         fplh::parallel_run((int)pieces.size(), [&](int i) {
             if (pieces[i].empty()) return;
@@ -168,6 +171,7 @@ static Outputs open_outputs(const Options& opt, const string& bamReadGroups = st
     o.gzLevel = min(9, max(1, opt.compression));
     o.keepTags = opt.keepTags;
     o.keepMods = opt.keepMods;
+    o.keepMoves = opt.keepMoves;
     o.comments = opt.commentTags ? &opt.commentSel : nullptr;
     o.fout.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);
     o.ffail.write_bam_header(o.gzLevel, opt.keepTags ? &bamReadGroups : nullptr);

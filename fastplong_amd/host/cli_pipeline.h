@@ -294,9 +294,12 @@ void Pipeline::enable_device_gzip() {
     if (bamOut && opt.keepTags) eligible = eligible && api.set_bam_tags != nullptr;
     /* --keep_mods: ... and fpl_set_bam_mods, in the same way */
     if (bamOut && opt.keepMods) eligible = eligible && api.set_bam_mods != nullptr;
+    /* --keep_moves: ... and fpl_set_bam_moves */
+    if (bamOut && opt.keepMoves) eligible = eligible && api.set_bam_moves != nullptr;
     if (bamOut) eligible = eligible && opt.deviceGzip && (in.textMode || facts.bam) && (devBamOut = frame_on_all(api.set_gzip_records, ctxs));
     if (bamOut && opt.keepTags && devBamOut &&
-        !(enable_on_all(api.set_bam_tags, true, ctxs) && (!opt.keepMods || enable_on_all(api.set_bam_mods, true, ctxs)))) { /* (a context refused: the host's form) */
+        !(enable_on_all(api.set_bam_tags, true, ctxs) && (!opt.keepMods || enable_on_all(api.set_bam_mods, true, ctxs)) &&
+          (!opt.keepMoves || enable_on_all(api.set_bam_moves, true, ctxs)))) { /* (a context refused: the host's form) */
         for (fpl_ctx* c : ctxs) (void)api.set_gzip_records(c, FPL_GZIP_FASTQ);
         eligible = devBamOut = false;
     }
@@ -716,8 +719,8 @@ void Pipeline::format_stage(int f) {
             /* --keep_tags: which input record every record of the pieces came from, by the formatter's own order */
             const fplh::FragmentList* fl = opt.fragmentMode ? &w->frags : nullptr;
             const bool tagOut = out.keepTags && out.fout && out.fout.bam && !w->dev_gz, tagFailed = out.keepTags && toFailed && out.ffail.bam;
-            if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, out.keepMods);
-            if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, out.keepMods);
+            if (tagOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, out.keepMods, out.keepMoves);
+            if (tagFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, out.keepMods, out.keepMoves);
             /* --comment_tags: the same lists, with re-indexing on, for the outputs that are FASTQ text; in front of the deflate */
             const bool noteOut = out.comments && w->batch.bam_backed && out.fout && !out.fout.bam && !w->dev_gz;
             const bool noteFailed = out.comments && w->batch.bam_backed && toFailed && !out.ffail.bam;

@@ -101,10 +101,10 @@ int format_hook(void* bv, const fpl_read_result* res, const fplh::FragmentList* 
    its results (and, with n_frags != ~0u, the fragment list of a --break / --mask run) given by the caller; formatted in `threads`
    pieces, the sources derived (bam_tag_sources), the pieces converted (pieces_to_bam_records).  out / failed: the uncompressed
    records of --out / --failed_out; stats: four counts each.  -1: the file did not read to its end as one batch of n reads.
-   mods: --keep_mods, with its four counts each in mod_stats */
+   mods: --keep_mods, with its four counts each in mod_stats; moves: --keep_moves, the same in move_stats */
 int bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n, const fpl_fragment* frags,
                  uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out, uint64_t* out_len, char** failed,
-                 uint64_t* failed_len, uint64_t* stats, bool mods, uint64_t* mod_stats) {
+                 uint64_t* failed_len, uint64_t* stats, bool mods, uint64_t* mod_stats, bool moves = false, uint64_t* move_stats = nullptr) {
     fplh::BamReader rd(path);
     if (!rd.ok()) return -1;
     Batch b;
@@ -123,13 +123,15 @@ int bam_tag_form(const char* path, const uint8_t* seq, const uint8_t* qual, cons
     std::vector<std::string> o, f;
     fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
     std::vector<fplh::BamTagSrc> so, sf;
-    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so, mods);
-    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf, mods);
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, false, so, mods, moves);
+    fplh::bam_tag_sources(b, res, 0, n, fragments ? &fl : nullptr, true, sf, mods, moves);
     for (int k = 0; k < 8; k++) stats[k] = 0;
     if (mod_stats)
         for (int k = 0; k < 8; k++) mod_stats[k] = 0;
-    fplh::pieces_to_bam_records(o, so, stats, mod_stats);
-    fplh::pieces_to_bam_records(f, sf, stats + 4, mod_stats ? mod_stats + 4 : nullptr);
+    if (move_stats)
+        for (int k = 0; k < 8; k++) move_stats[k] = 0;
+    fplh::pieces_to_bam_records(o, so, stats, mod_stats, move_stats);
+    fplh::pieces_to_bam_records(f, sf, stats + 4, mod_stats ? mod_stats + 4 : nullptr, move_stats ? move_stats + 4 : nullptr);
     std::string oo, ff;
     for (auto& x : o) oo += x;
     for (auto& x : f) ff += x;
@@ -344,6 +346,14 @@ int fplh_bam_mod_form(const char* path, const uint8_t* seq, const uint8_t* qual,
                       const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
                       uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats, uint64_t* mod_stats) {
     return bam_tag_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, out, out_len, failed, failed_len, stats, true, mod_stats);
+}
+/* _move_form: with --keep_moves, and with --keep_mods beside it where mods != 0; four counts each in mod_stats and move_stats */
+int fplh_bam_move_form(const char* path, const uint8_t* seq, const uint8_t* qual, const fpl_read_result* res, uint32_t n,
+                       const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs, int threads, char** out,
+                       uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats, int mods, uint64_t* mod_stats, int moves,
+                       uint64_t* move_stats) {
+    return bam_tag_form(path, seq, qual, res, n, frags, n_frags, regs, n_regs, threads, out, out_len, failed, failed_len, stats, mods != 0, mod_stats,
+                        moves != 0, move_stats);
 }
 /* test hooks of --comment_tags.  _form: the host form as the CLI runs it (bam_comment_form above; tags: 2 * n_tags bytes, n_tags -1:
    every field); _text: the rule's text of the tag bytes p[0, len) under a selection, and its three counts (fields, bytes, left

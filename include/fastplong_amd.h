@@ -527,6 +527,29 @@ int fpl_set_bam_mods(fpl_ctx* ctx, int on);
 int fpl_get_bam_mod_stats(fpl_ctx* ctx, uint64_t* out);
 
 /*
+ * The move table mv and its ts re-indexed in such records where they are trimmed or split (README "BAM output", --keep_moves; the
+ * rule and its wording: csrc/bam_move_rules.h).  FPL_ABI_VERSION stays 10: both calls are found by symbol lookup; a caller of a
+ * library without them writes such records on the host.
+ *
+ *   fpl_set_bam_moves  per context; takes effect with the NEXT submission and is ignored unless fpl_set_bam_tags is on.  It is
+ *                      independent of fpl_set_bam_mods: either switch decides its own fields.  A changed output record of a
+ *                      MOVE-RE-INDEXABLE input record gets, in the places of its mv and ts fields, the table cut to the moves of
+ *                      its bases [frag_start, + frag_len) of the read -- the stride in front, leading zeros kept where frag_start
+ *                      is 0 -- and ts advanced by stride x the moves cut from the front, widened to S or I where its own type
+ *                      does not hold the value.  Move-re-indexable: flag without 0x10, no --break / --mask, exactly one mv of type
+ *                      B:c or B:C with a stride in 1..127 and moves of 0 and 1 of which l_seq are 1, at most one ts of an integer
+ *                      type that is not negative.  A record with a table that is not re-indexable, and an output record whose new
+ *                      ts passes 2^32 - 1 or whose two fields would grow, is written as without the switch.  A record's tag bytes
+ *                      never exceed its input region: the bound of fpl_set_bam_tags stands.
+ *   fpl_get_bam_move_stats  out[4], since the context was made: output records re-indexed; changed output records with a table
+ *                      that were not re-indexable and lost it; table entries (moves) kept; entries cut away.  It waits like
+ *                      fpl_get_bam_tag_stats, whose counts keep their meaning: a changed record counts as one that kept every
+ *                      field when every positional field it has was re-indexed by one of the two switches.
+ */
+int fpl_set_bam_moves(fpl_ctx* ctx, int on);
+int fpl_get_bam_move_stats(fpl_ctx* ctx, uint64_t* out);
+
+/*
  * The auxiliary fields of a BAM input's records as COMMENTS behind the names of a gzip batch's FASTQ text (README "Tags as FASTQ
  * comments", --comment_tags; the rule and its wording: csrc/bam_comment_rules.h).  FPL_ABI_VERSION stays 10: both calls are found
  * by symbol lookup; a caller of a library without them formats such batches on the host.

@@ -12,7 +12,12 @@ writes that again).  The wall time printed holds the upload, the parse, the per-
 ONT-like reads with adapters (median 5 kb, a middle adapter in three of ten) that carry generated modification calls -- C+mh? at
 CpGs, A+a. at every fourth A, a sparse N+n group --, submitted three times through Engine.submit_bam(gzip=True) with set_bam_tags
 and set_bam_mods (k_bam_tags_mods, k_bam_mods_plan, k_bamout_compose_bam_mods), or with --tags-only with set_bam_tags alone
-(k_bam_tags, k_bamout_compose_bam_tags): the form to compare with in the same session."""
+(k_bam_tags, k_bamout_compose_bam_tags): the form to compare with in the same session.
+
+`--moves [Mbases]` / `--moves --tags-only [Mbases]`: the --keep_moves leg (fastplong_amd/csrc/bam_moves.h).  The --mods batch shape
+with move tables of about 2 entries a base (stride 6, 1 to 3 entries per base), ts and ns in place of the modification calls,
+with set_bam_tags and set_bam_moves (k_bam_tags_moves, k_bam_moves_plan, k_bamout_compose_bam_moves) or, with --tags-only, with
+set_bam_tags alone.  It prints the table bytes of the candidate records: what k_bam_moves_plan reads once."""
 import os
 import sys
 import time
@@ -60,9 +65,10 @@ def main(mbases=1000, L=10_000, bam=False):
     eng.close()
 
 
-def mods_main(mbases=100, mods=True):
+def mods_main(mbases=100, mods=True, moves=None):
     from fastplong_amd import synth
     from tests import bam_mod_cases as mc
+    from tests import bam_move_cases as vc
     from tests import bamio, hostio
     L = 5000
     pool = 256  # distinct reads: generating the calls in Python is the slow part; the kernels do not care that reads repeat
@@ -74,7 +80,11 @@ def mods_main(mbases=100, mods=True):
         cpg = [k for k, p in enumerate(occ) if p + 1 < len(codes) and codes[p + 1] == 4]
         spec = [(b"C+mh?", [m - (cpg[j - 1] + 1 if j else 0) for j, m in enumerate(cpg)]), (b"A+a.", mc.every(codes, b"A", 4, 3)),
                 (b"N+n", mc.every(codes, b"N", 997, 11))]
-        encoded.append((len(codes), bamio.encode_record(b"read%d" % i, 4, codes, q, tags=mc.fields_of(codes, spec, rng))))
+        tags, table = mc.fields_of(codes, spec, rng) if moves is None else None, 0
+        if moves is not None:
+            table = int(rng.integers(1, 4, len(codes)).sum()) + 2
+            tags = vc.fields_of(vc.table(len(codes), table, rng, lead=2), ts=(b"i", 10 + i))
+        encoded.append((len(codes), bamio.encode_record(b"read%d" % i, 4, codes, q, tags=tags), table))
     n = max(1, mbases * 1_000_000 // L)
     raw, starts, offs = bytearray(), [], [0]
     for i in range(n):
@@ -86,7 +96,9 @@ def mods_main(mbases=100, mods=True):
                         synth.END_ADAPTER, device=0, max_cycles=int(max(e[0] for e in encoded)) + 64)
     eng.set_gzip_records(True)
     eng.set_bam_tags(True)
-    eng.set_bam_mods(mods)
+    eng.set_bam_mods(mods and moves is None)
+    if moves is not None:
+        eng.set_bam_moves(moves)
     buf = eng.pinned_array(len(raw))
     buf[:] = np.frombuffer(bytes(raw), np.uint8)
     res = np.zeros(n, abi.RESULT_DTYPE)
@@ -95,15 +107,23 @@ def mods_main(mbases=100, mods=True):
         eng.submit_bam(buf, starts, offs, res=res, gzip=True)
         out = eng.wait()
         print("batch %d (%s): %.3f s wall, %d records of %d bytes, %.3f Gbases -> %d bytes of BGZF blocks; %d split reads" % (
-            k, "--keep_mods" if mods else "--keep_tags alone", time.time() - t0, n, len(raw), int(offs[-1]) / 1e9, len(out), int((res["n_frag"] == 2).sum())))
+            k, "--keep_moves" if moves else "--keep_mods" if mods and moves is None else "--keep_tags alone", time.time() - t0, n, len(raw), int(offs[-1]) / 1e9, len(out), int((res["n_frag"] == 2).sum())))
     print("tag counts: %s; modification counts: %s" % (eng.bam_tag_stats(), eng.bam_mod_stats()))
+    if moves is not None:
+        whole = (res["n_frag"] == 1) & (res["code"][:, 0] == 0) & (res["frag_start"][:, 0] == 0) & (res["frag_len"][:, 0] == np.diff(offs.astype(np.int64)))
+        cand = ~whole & (res["dropped"] == 0) & ((res["code"][:, 0] == 0) | ((res["n_frag"] == 2) & (res["code"][:, 1] == 0)))
+        table_bytes = int(sum(encoded[i % pool][2] for i in np.flatnonzero(cand)))
+        print("move counts: %s; %d candidate records, their tables %d bytes: read once at 8 TB/s in %.4f ms" % (
+            eng.bam_move_stats(), int(cand.sum()), table_bytes, table_bytes / 8e12 * 1e3))
     eng.close()
 
 
 if __name__ == "__main__":
-    flags = ("--bam", "--mods", "--tags-only")
+    flags = ("--bam", "--mods", "--moves", "--tags-only")
     args = [a for a in sys.argv[1:] if a not in flags]
-    if "--mods" in sys.argv[1:]:
+    if "--moves" in sys.argv[1:]:
+        mods_main(*(int(a) for a in args[:1]), mods=False, moves="--tags-only" not in sys.argv[1:])
+    elif "--mods" in sys.argv[1:]:
         mods_main(*(int(a) for a in args[:1]), mods="--tags-only" not in sys.argv[1:])
     else:
         main(*(int(a) for a in args[:1]), bam="--bam" in sys.argv[1:])

@@ -324,6 +324,16 @@ int fpl_get_bam_comment_stats(fpl_ctx* ctx, uint64_t* out) {
     for (int k = 0; k < 4; k++) out[k] = 0;
     return FPL_OK;
 }
+/* (nor mv and ts: the host writes every record of a --keep_moves run) */
+int fpl_set_bam_moves(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    return on ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
+int fpl_get_bam_move_stats(fpl_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return FPL_ERR_ARG;
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    return FPL_OK;
+}
 /* (BGZF inflate: no device, so no inflater -- a host that finds the calls gets no handle and inflates itself) */
 fpl_inflater* fpl_inflater_create(int32_t) { return nullptr; }
 int fpl_inflate_bgzf(fpl_inflater*, const uint8_t*, uint64_t, fpl_bgzf_block*, uint32_t n_blocks, uint8_t*, uint64_t) {
