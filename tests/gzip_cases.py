@@ -13,11 +13,14 @@ chunks of 1 KiB and 4 KiB; the same levels at zlib's default memLevel (blocks of
 
 describe() is a small deflate reader of its own (block types, their distance codes, the largest distance, the 258-at-1 matches):
 what a stream's name promises is checked with it on the CPU (tests/test_gzip_inflate_emu.py)."""
+import json
+import os
 import zlib
 
 import numpy as np
 
 from fastplong_amd import synth
+from tests import bgzf_cases
 from tests.bgzf_cases import (CL_ORDER, DIST_BASE, DIST_EXTRA, FIXED_DIST, FIXED_LIT, LEN_BASE, LEN_EXTRA, Bits, canonical, dynamic_block,
                               fixed_block, stored_block)
 
@@ -219,6 +222,7 @@ def doubt_cases(seed=3):
 class Run:
     def __init__(self, case):
         self.case, self.bit, self.out, self.windows, self.refused, self.final, self.done = case, 0, b"", [], 0, False, False
+        self.log = []  # every result that came back, refused ones too: RECORD_FIELDS of each
 
     def job(self):
         c, at = self.case, self.bit >> 3
@@ -227,6 +231,7 @@ class Run:
 
     def take(self, r):
         """one result (rc, status, out_bytes, end_bit, crc32, final, data)"""
+        self.log.append([int(r[k]) for k in RECORD_FIELDS])
         stuck = r["rc"] == 0 and r["status"] == 0 and not r["final"] and r["end_bit"] <= (self.bit & 7)
         if r["rc"] != 0 or r["status"] != 0 or stuck:
             self.refused, self.done = self.refused + 1, True  # (the caller inflates the rest itself)
@@ -277,6 +282,77 @@ def check_doubt_list(runs):
             assert r.case.whole and r.out == want, r.case.name
         if r.case.out_short:
             assert len(r.out) <= len(want) - r.case.out_short and not r.final, r.case.name
+
+
+# ---------------------------------------------------------------- what the decoder answers, pinned
+# tests/golden/gzip_window_results.json: the decoder's own answers (this project's code on the emulator, written with
+# `python -m tests.gzip_cases --record`), so that a change which moves a check, and with it a status or the end of a window, shows.
+# Names and integers only: the streams are rebuilt from their seeds.
+RECORD_FIELDS = ("rc", "status", "out_bytes", "end_bit", "crc32", "final", "chunks")
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gzip_window_results.json")
+
+
+def stream_cases():
+    """the hand-made and the refused streams of the BGZF tests (tests/bgzf_cases.py), for this decoder"""
+    return bgzf_cases.refuse_cases() + bgzf_cases.hand_cases()
+
+
+def stream_jobs():
+    """... each as one window from bit 0 with no dictionary"""
+    return [dict(comp=c.payload, start_bit=0, dict=b"", out_cap=len(c.data) + 64, chunk_bytes=1024) for c in stream_cases()]
+
+
+def window_results(doubt_runs, stream_res):
+    """the runs of doubt_cases() and the results of stream_jobs() in the form of the record"""
+    names = [r.case.name for r in doubt_runs]
+    assert len(set(names)) == len(names)
+    return {"fields": list(RECORD_FIELDS),
+            "doubt": {"names": names, "windows": [r.log for r in doubt_runs]},
+            "streams": {"names": [c.name for c in stream_cases()], "results": [[int(r[k]) for k in RECORD_FIELDS] for r in stream_res]}}
+
+
+def check_doubt_record(doubt_runs):
+    want = json.load(open(RECORD))
+    assert want["fields"] == list(RECORD_FIELDS)
+    assert [r.case.name for r in doubt_runs] == want["doubt"]["names"]
+    for r, w in zip(doubt_runs, want["doubt"]["windows"]):
+        assert r.log == w, (r.case.name, r.log, w)
+
+
+def check_stream_record(stream_res):
+    want = json.load(open(RECORD))
+    assert want["fields"] == list(RECORD_FIELDS)
+    cases = stream_cases()
+    assert [c.name for c in cases] == want["streams"]["names"] and len(stream_res) == len(cases)
+    for c, r, w in zip(cases, stream_res, want["streams"]["results"]):
+        assert [int(r[k]) for k in RECORD_FIELDS] == w, (c.name, r, w)
+
+
+def check_stream_rules(stream_res):
+    """what holds by rule for the results of stream_jobs(): where this decoder and the BGZF one must differ, and where not"""
+    by = {c.name: (c, r) for c, r in zip(stream_cases(), stream_res)}
+    c, r = by["refuse/single_distance_code"]  # zlib's incomplete distance set: taken here, refused there
+    assert r["rc"] == 0 and r["status"] == 0 and r["final"] and r["data"] == c.data and len(c.data) > 0, r
+    c, r = by["refuse/distance_before_start"]  # the marker has nothing to resolve against
+    assert r["rc"] == 0 and r["status"] != 0 and r["data"] == b"", r
+    hand = [(c, r) for c, r in by.values() if c.name.startswith("hand/")]
+    assert len(hand) >= 15
+    for c, r in hand:
+        assert c.zlib_ok and r["rc"] == 0 and r["status"] == 0 and r["final"] and r["data"] == c.data, (c.name, r["status"])
+        assert r["crc32"] == zlib.crc32(c.data) and r["end_bit"] + 7 >> 3 == len(c.payload), c.name
+
+
+def record(batch_call):
+    """writes the record: to be run on the emulator, at a commit whose decoder is the one to hold on to"""
+    got = window_results(run_members(doubt_cases(), batch_call), batch_call(stream_jobs()))
+    with open(RECORD, "w") as f:
+        f.write("{\n \"fields\": %s,\n" % json.dumps(got["fields"]))
+        for key, rows in (("doubt", "windows"), ("streams", "results")):
+            f.write(" \"%s\": {\n  \"names\": %s,\n  \"%s\": [\n" % (key, json.dumps(got[key]["names"]), rows))
+            f.write(",\n".join("   " + json.dumps(v, separators=(",", ":")) for v in got[key][rows]))
+            f.write("\n  ]\n }%s\n" % ("," if key == "doubt" else ""))
+        f.write("}\n")
+    return got
 
 
 # ---------------------------------------------------------------- a deflate reader of its own
@@ -364,3 +440,16 @@ def describe(comp):
             d["last_block_bits"] = pos - at
             d["end_bit"] = pos
             return d
+
+
+if __name__ == "__main__":
+    import sys
+
+    from tests.emu_gzip import build as emu
+
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: python -m tests.gzip_cases --record")
+    emu.build()
+    got = record(emu.inflate)
+    print("%s: %d windows of %d runs, %d streams" % (RECORD, sum(len(w) for w in got["doubt"]["windows"]), len(got["doubt"]["names"]),
+                                                     len(got["streams"]["names"])))

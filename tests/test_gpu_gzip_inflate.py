@@ -54,6 +54,7 @@ def test_zlib_writes_these(inflater):
 def test_must_not_be_believed(inflater):
     runs = gc.run_members(gc.doubt_cases(), caller(inflater))
     gc.check_doubt_list(runs)
+    gc.check_doubt_record(runs)  # every window's status and end are the emulator's (tests/golden/gzip_window_results.json)
     by = {r.case.name: r for r in runs}
     for ch in gc.CHUNKS:
         r = by["right_dict/c%d" % ch]
@@ -62,6 +63,13 @@ def test_must_not_be_believed(inflater):
         assert e.refused or (e.final and e.out == e.case.data)
         assert not by["out_cap_short/c%d" % ch].final
     assert all(not r.final for r in runs if r.case.name.startswith("cut/"))
+
+
+def test_hand_made_and_refused_streams_of_the_bgzf_tests(inflater):
+    """each as one window: the recorded results, and what holds by rule where this decoder and k_bgzf_inflate differ"""
+    res = caller(inflater)(gc.stream_jobs())
+    gc.check_stream_record(res)
+    gc.check_stream_rules(res)
 
 
 def test_eight_megabytes_at_the_default_sizes(inflater):

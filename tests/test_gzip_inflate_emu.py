@@ -57,8 +57,20 @@ def test_zlib_writes_these():
             assert max(w["chunks"] for w in r.windows) >= 2, r.case.name
 
 
-def test_must_not_be_believed():
-    runs = gc.run_members(gc.doubt_cases(), batch_call)
+@pytest.fixture(scope="module")
+def doubt_runs(built):
+    """list (b) through its windows, once for the tests that look at it"""
+    return gc.run_members(gc.doubt_cases(), batch_call)
+
+
+@pytest.fixture(scope="module")
+def stream_res(built):
+    """the hand-made and the refused streams of the BGZF tests, one window each"""
+    return batch_call(gc.stream_jobs())
+
+
+def test_must_not_be_believed(doubt_runs):
+    runs = doubt_runs
     gc.check_doubt_list(runs)
     by = {r.case.name: r for r in runs}
     for ch in gc.CHUNKS:
@@ -68,6 +80,30 @@ def test_must_not_be_believed():
         assert e.refused or (e.final and e.out == e.case.data)
         assert not by["out_cap_short/c%d" % ch].final
     assert all(not r.final for r in runs if r.case.name.startswith("cut/"))
+
+
+def test_recorded_window_results_are_this_run_s(doubt_runs, stream_res):
+    """tests/golden/gzip_window_results.json: every window's rc, status, byte count, end bit, CRC-32, final flag and chunk count, of
+    list (b) and of the BGZF tests' hand-made and refused streams.  A check that moved inside the decoder shows here."""
+    gc.check_doubt_record(doubt_runs)
+    gc.check_stream_record(stream_res)
+
+
+def test_the_two_decoders_differ_where_they_must_and_nowhere_else(stream_res):
+    """the same streams through this decoder and through k_bgzf_inflate (tests/emu_bgzf): the single 1-bit distance code, the
+    distance that reaches before the output's start, and the hand-made streams both take"""
+    from tests import bgzf_cases as bc
+    from tests.emu_bgzf import build as emu_bgzf
+
+    emu_bgzf.build()
+    cases = gc.stream_cases()
+    gc.check_stream_rules(stream_res)
+    comp, blocks, out = bc.pack(cases, 12)
+    got, done = emu_bgzf.inflate(comp, blocks, out)
+    bc.check(cases, blocks, got, done["status"])  # (a status 0 there means zlib's bytes: the same as this decoder's)
+    st = {c.name: int(s) for c, s in zip(cases, done["status"])}
+    assert st["refuse/single_distance_code"] == 1 and st["refuse/distance_before_start"] == 1  # FPL_BGZF_MALFORMED
+    assert all(s == 0 for n, s in st.items() if n.startswith("hand/"))
 
 
 def test_eight_megabytes_at_the_default_sizes():
