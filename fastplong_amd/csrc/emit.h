@@ -17,12 +17,17 @@
  * The records are the caller's memory and may hold anything.  k_emit_count vouches for every window it counts
  * (frag_start + frag_len inside the read), k_emit_scan for the totals against the capacities; the fill and the gather run
  * only behind a zero status and then cannot read outside a read or write outside the capacities.
+ *
+ * With fpl_set_fragment_output on a --break / --mask context the output reads are the ordered fragments of the context's last
+ * batch (frag_index.h): k_emit_count_frag / k_emit_fill_frag in place of the count and the fill, k_emit_mask behind the gather
+ * (at the end of this file).
  */
 #ifndef FPL_EMIT_H
 #define FPL_EMIT_H
 
 #include "../../include/fastplong_amd.h"
 #include "dev_prims.h"
+#include "frag_index.h"
 
 namespace fpl {
 
@@ -329,6 +334,123 @@ k_emit_gather(const u8* __restrict__ seq, const u8* __restrict__ qual, const uin
             if (r >= n_out) r = n_out - 1; /* (lanes behind the end of the output) */
             cur = uniform_u32(shfl_u32(r, 63));
             if (p < t1) em_copy16(seq, qual, off_out, from, seq_out, qual_out, p, t1, r);
+        }
+    }
+}
+
+/* ---- the fragment forms (fpl_set_fragment_output): the output reads of a --break / --mask batch ----
+   The reads are the batch's fragment list in the order frag_index.h makes: k_emit_count_frag and k_emit_fill_frag are the count
+   and the fill with a lane per ordered fragment -- blocks of EM_LAYOUT_READS fragments, as many as the list's CAPACITY asks for
+   (how many fragments there are only the device knows; the blocks behind them count nothing) --, k_emit_scan and k_emit_gather
+   run unchanged on what they leave, and k_emit_mask writes N over the regions behind the gather.  The caller's records say which
+   reads are dropped and nothing else. */
+struct EmitFrag {
+    bool take, bad;
+    fpl_fragment f;
+};
+__device__ __forceinline__ EmitFrag em_frag(const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_reads,
+                                            const fpl_fragment* __restrict__ frags, const u32* __restrict__ order, u32 j, u32 n) {
+    EmitFrag e = {};
+    const u32 ent = frag_entry(order, j, n);
+    if (ent == FI_NONE) return e;
+    e.f = frags[ent];
+    if (e.f.code != FPL_PASS_FILTER || e.f.read >= n_reads || res[e.f.read].dropped) return e;
+    const u64 o0 = off[e.f.read], o1 = off[(u64)e.f.read + 1];
+    e.take = true;
+    e.bad = (u64)e.f.start + e.f.len > (o1 >= o0 ? o1 - o0 : 0);
+    return e;
+}
+__global__ void __launch_bounds__(EM_LAYOUT_READS)
+k_emit_count_frag(const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_reads, const fpl_fragment* __restrict__ frags,
+                  const u32* __restrict__ order, const FragIndex* __restrict__ fi, u32* __restrict__ blk_cnt, u64* __restrict__ blk_bytes,
+                  u32* __restrict__ blk_max) {
+    __shared__ u32 w_cnt[EM_LAYOUT_READS / 64], w_max[EM_LAYOUT_READS / 64];
+    __shared__ u64 w_bytes[EM_LAYOUT_READS / 64];
+    const u32 n = frag_index_len(fi);
+    const u64 j = (u64)blockIdx.x * EM_LAYOUT_READS + threadIdx.x;
+    EmitFrag e = {};
+    if (j < n) e = em_frag(off, res, n_reads, frags, order, (u32)j, n);
+    const u32 len = e.take ? e.f.len : 0u;
+    const u32 cnt = wave_sum_u32((e.take ? 1u : 0u) | (e.bad ? 1u << 16 : 0u));
+    const u32 mx = wave_max_u32(len);
+    const u64 by = em_wave_scan_incl_u64(len);
+    if (lane_id() == 63) {
+        w_cnt[wave_in_block()] = cnt;
+        w_max[wave_in_block()] = mx;
+        w_bytes[wave_in_block()] = by;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 c = 0, m = 0;
+        u64 b = 0;
+        for (int k = 0; k < EM_LAYOUT_READS / 64; k++) {
+            c += w_cnt[k];
+            m = max(m, w_max[k]);
+            b += w_bytes[k];
+        }
+        blk_cnt[blockIdx.x] = (c & 0xFFFFu) | (c >> 16 ? EM_BAD : 0u);
+        blk_max[blockIdx.x] = m;
+        blk_bytes[blockIdx.x] = b;
+    }
+}
+/* ent[j]: the list entry of output read j (k_emit_mask finds its regions there); break_no may be nullptr.  A status of the index
+   becomes bit 2 of the info record here: the count saw an empty list, so everything else in the record is zero already */
+__global__ void __launch_bounds__(EM_LAYOUT_READS)
+k_emit_fill_frag(const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_reads, const fpl_fragment* __restrict__ frags,
+                 const u32* __restrict__ order, const FragIndex* __restrict__ fi, const u32* __restrict__ blk_cnt,
+                 const u64* __restrict__ blk_bytes, fpl_emit_info* __restrict__ info, uint64_t* __restrict__ off_out, u32* __restrict__ src,
+                 u8* __restrict__ kind, uint16_t* __restrict__ break_no, EmitFrom* __restrict__ from, u32* __restrict__ ent) {
+    __shared__ u32 w_cnt[EM_LAYOUT_READS / 64];
+    __shared__ u64 w_bytes[EM_LAYOUT_READS / 64];
+    if (fi->status) { /* block-uniform */
+        if (blockIdx.x == 0 && threadIdx.x == 0) info->status |= 4u;
+        return;
+    }
+    if (info->status) return; /* block-uniform: nothing of a refused batch is written */
+    const u32 n = fi->n;
+    const u64 j0 = (u64)blockIdx.x * EM_LAYOUT_READS + threadIdx.x;
+    EmitFrag e = {};
+    if (j0 < n) e = em_frag(off, res, n_reads, frags, order, (u32)j0, n);
+    const u64 y = e.take ? e.f.len : 0u;
+    const u32 c = e.take ? 1u : 0u;
+    const u32 ci = wave_scan_incl_u32(c);
+    const u64 yi = em_wave_scan_incl_u64(y);
+    if (lane_id() == 63) {
+        w_cnt[wave_in_block()] = ci;
+        w_bytes[wave_in_block()] = yi;
+    }
+    __syncthreads();
+    u64 j = (u64)blk_cnt[blockIdx.x] + ci - c;
+    u64 at = blk_bytes[blockIdx.x] + yi - y;
+    for (int k = 0; k < wave_in_block(); k++) {
+        j += w_cnt[k];
+        at += w_bytes[k];
+    }
+    if (!e.take) return;
+    from[j] = off[e.f.read] + e.f.start - at;
+    off_out[j + 1] = at + e.f.len;
+    ent[j] = order[j0];
+    if (src) src[j] = e.f.read;
+    if (kind) kind[j] = e.f.kind;
+    if (break_no) break_no[j] = e.f.break_no;
+}
+/* behind the gather, on its stream: a wave per output read whose fragment has regions writes N over them in seq_out
+   (frag_clip_region: the clipping of the host's append_masked).  The gather's stores are done -- a kernel boundary --, so the
+   order of the two writes to a masked byte is not a question. */
+__global__ void __launch_bounds__(EM_GATHER_THREADS)
+k_emit_mask(const fpl_fragment* __restrict__ frags, const fpl_region* __restrict__ regs, const u32* __restrict__ ent,
+            const uint64_t* __restrict__ off_out, const fpl_emit_info* __restrict__ info, u8* __restrict__ seq_out) {
+    if (info->status) return;
+    const u32 n_out = info->n_out;
+    const u32 wave = (u32)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), n_waves = (u32)((gridDim.x * blockDim.x) >> 6);
+    const u32 lane = (u32)lane_id();
+    for (u32 j = wave; j < n_out; j += n_waves) { /* wave-uniform */
+        const fpl_fragment f = frags[ent[j]];
+        u8* const d = seq_out + off_out[j];
+        for (u32 k = 0; k < f.region_count; k++) {
+            u32 a, l;
+            if (!frag_clip_region(regs[f.region_first + k], f.start, f.len, a, l)) continue;
+            for (u32 i = lane; i < l; i += 64) d[a + i] = (u8)'N';
         }
     }
 }

@@ -38,6 +38,11 @@
  *   k_gz_compact      unchanged
  * Worst case: gz_len <= total + GZ_SLACK * n_blocks + GZ_BGZF_EXTRA * ceil(total / GZ_STRIPE) (beside GZ_STRIPE below).
  *
+ * The fragment forms (fpl_set_fragment_output): a context with break_enabled / mask_enabled writes from its fragment list, whose
+ * order frag_index.h makes on the device.  k_gz_layout_frag[_bam] / k_gz_compose_frag[_bam] run the same scan, the same cuts and
+ * the same wave copy with a lane / a wave per ordered FRAGMENT; the bytes are format_range's with a fragment list ("r<i>-" in the
+ * name, the fragment's regions as N).  Everything from k_gz_block on runs unchanged.
+ *
  * The layout body is also templated on the FORM of the composed bytes (GzFastqForm here); csrc/bam_emit.h has the form of unaligned
  * BAM records (fpl_set_gzip_records), a compose kernel of its own, and runs the BGZF block kernels on what it composes.
  */
@@ -46,6 +51,7 @@
 
 #include "../../include/fastplong_amd.h"
 #include "dev_prims.h"
+#include "frag_index.h"
 
 namespace fpl {
 
@@ -61,7 +67,9 @@ constexpr u32 GZ_MEMBER_EXTRA = 10 + 5 + 8;   /* gzip header, final empty block,
    cuts, whatever their compressed sizes.  Worst case of one BGZF block: a stripe holds at most 3 + 2 * ceil(49 152 / 2 050) + 1 =
    52 deflate blocks (its three multiples of GZ_B, two forced starts per fragment of at least GZ_L - 1 bases -- such a fragment
    writes at least 2 * (GZ_L - 1) + 4 = 2 050 bytes --, one for what is left of a fragment that began in the stripe before), each
-   grows by at most GZ_SLACK, so the block stays below 49 152 + 5 * 53 + 31 = 49 448 bytes: far inside BGZF's 65 536. */
+   grows by at most GZ_SLACK, so the block stays below 49 152 + 5 * 53 + 31 = 49 448 bytes: far inside BGZF's 65 536.
+   The fragment forms (k_gz_layout_frag) keep the bound: their forced cuts come from the same rule (gz_frag_cuts), so a forced cut
+   still needs a fragment of at least GZ_L - 1 bases -- 2 050 bytes of output and more, the "r<i>-" of its name besides. */
 constexpr u32 GZ_STRIPE = 3 * GZ_B;
 constexpr u32 GZ_BGZF_HEAD = 18;                       /* gzip header with the BC extra field */
 constexpr u32 GZ_BGZF_EXTRA = GZ_BGZF_HEAD + 5 + 8;    /* header, final empty block, CRC-32 + ISIZE: per BGZF block */
@@ -93,6 +101,16 @@ inline u64 gz_blocks_bound(u64 text_bytes, u64 n_rec) { return gz_total_bound(te
    the '+' line and four line ends besides its bases and qualities */
 inline u64 gz_bam_total_bound(u64 n_bases, u64 n_rec) { return 4 * n_bases + 2 * (255 + 23 + 6) * n_rec; }
 inline u64 gz_bam_blocks_bound(u64 n_bases, u64 n_rec) { return gz_bam_total_bound(n_bases, n_rec) / GZ_B + 2 + 4 * n_rec; }
+/* the fragment forms (fpl_set_fragment_output): a read's name is written once per fragment, so the bounds above do not hold.  By
+   the capacity of the fragment list (break_mask_caps, which the host knows without asking the device): the fragments of a read
+   are disjoint windows of it, every fragment writes its name line (1 + 7 + 23 + the name), the '+' line and four line ends -- 320
+   bytes cover a BAM's 254-byte name; a text batch whose name and '+' lines are longer than that on the average of its fragments
+   runs out of block slots, which is a status of the layout --, and only a fragment of at least GZ_L - 1 bases forces cuts */
+inline u64 gz_frag_total_bound(u64 n_bases, u64 frag_cap) { return 2 * n_bases + 320 * frag_cap; }
+inline u64 gz_frag_blocks_bound(u64 n_bases, u64 frag_cap) {
+    const u64 forced = n_bases / (GZ_L - 1);
+    return gz_frag_total_bound(n_bases, frag_cap) / GZ_B + 2 + 2 * (forced < frag_cap ? forced : frag_cap);
+}
 
 /* ---- CRC-32 arithmetic (reflected: bit 31 is x^0) ---- */
 __device__ __forceinline__ u32 gz_mulmod(u32 a, u32 b) { /* a * b mod P */
@@ -229,6 +247,17 @@ __device__ __forceinline__ void gz_cuts(u64 s, u64 e, bool force, F&& emit) {
     if (force || s % GZ_B == 0) emit(s);
     for (u64 m = (s / GZ_B + 1) * GZ_B; m < e; m += GZ_B) emit(m);
 }
+/* the block starts of one output read at o: a bytes of name + bases, b bytes of '+' + qualities.  THE forced-cut rule: a bases
+   line of at least GZ_L bytes (its line end counted) starts a block at its name line and another at its '+' line */
+template <class F>
+__device__ __forceinline__ void gz_frag_cuts(u64 o, u64 a, u64 b, u32 bases, F&& emit) {
+    if ((u64)bases + 1 >= GZ_L) {
+        gz_cuts(o, o + a, true, emit);
+        gz_cuts(o + a, o + a + b, true, emit);
+    } else {
+        gz_cuts(o, o + a + b, false, emit);
+    }
+}
 template <class Form = GzFastqForm, class Rec, class F>
 __device__ __forceinline__ void gz_read_cuts(const Rec& g, const fpl_read_result& r, u64 o, F&& emit) {
     if (r.dropped) return;
@@ -236,12 +265,7 @@ __device__ __forceinline__ void gz_read_cuts(const Rec& g, const fpl_read_result
         if (r.code[f] != FPL_PASS_FILTER) continue;
         u64 a, b;
         Form::frag_len(g, r, f, a, b);
-        if ((u64)r.frag_len[f] + 1 >= GZ_L) {
-            gz_cuts(o, o + a, true, emit);
-            gz_cuts(o + a, o + a + b, true, emit);
-        } else {
-            gz_cuts(o, o + a + b, false, emit);
-        }
+        gz_frag_cuts(o, a, b, r.frag_len[f], emit);
         o += a + b;
     }
 }
@@ -256,51 +280,74 @@ __device__ __forceinline__ u64 gz_scan_incl_u64(u64 v) {
     return incl;
 }
 
-/* one block.  rec_off[r] = where record r's output starts (n_rec + 1 entries), blk_start[b] = where deflate block b starts
+/* What a lane of the layout is: a record of the batch (GzReadItem) or, with fpl_set_fragment_output, one ordered fragment of its
+   --break / --mask list (GzFragItem below).  load(i): what the lane keeps; len(): the bytes it writes; cuts(): its block starts. */
+template <class Form, class Src>
+struct GzReadItem {
+    Src src;
+    const fpl_read_result* res;
+    struct State {
+        typename Src::Rec g;
+        fpl_read_result r;
+    };
+    __device__ __forceinline__ State load(u32 i) const {
+        State s;
+        s.g = src.rec(i);
+        Form::prep(s.g);
+        s.r = res[i];
+        return s;
+    }
+    __device__ __forceinline__ u64 len(const State& s) const {
+        u64 len = 0;
+        if (!s.r.dropped)
+            for (int f = 0; f < s.r.n_frag && f < 2; f++)
+                if (s.r.code[f] == FPL_PASS_FILTER) {
+                    u64 a, b;
+                    Form::frag_len(s.g, s.r, f, a, b);
+                    len += a + b;
+                }
+        return len;
+    }
+    template <class F>
+    __device__ __forceinline__ void cuts(const State& s, u64 o, F&& emit) const { gz_read_cuts<Form>(s.g, s.r, o, emit); }
+};
+
+/* one block.  rec_off[i] = where item i's output starts (n + 1 entries), blk_start[b] = where deflate block b starts
    (n_blocks + 1 entries, the last one the total) */
-template <class Form = GzFastqForm, class Src>
-__device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off,
-                                               u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
+template <class Item>
+__device__ __forceinline__ void gz_layout_scan(const Item& it, u32 n, u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap,
+                                               GzHeader* __restrict__ hdr) {
     __shared__ u64 wsum[16];
     __shared__ u64 carry_len, carry_blk;
     if (threadIdx.x == 0) carry_len = 0, carry_blk = 0;
     __syncthreads();
-    for (u32 base = 0; base < n_rec; base += 1024) { /* block-uniform */
+    for (u32 base = 0; base < n; base += 1024) { /* block-uniform */
         const u32 i = base + threadIdx.x;
-        typename Src::Rec g = {};
-        fpl_read_result r = {};
+        typename Item::State s = {};
         u64 len = 0;
-        if (i < n_rec) {
-            g = src.rec(i);
-            Form::prep(g);
-            r = res[i];
-            if (!r.dropped)
-                for (int f = 0; f < r.n_frag && f < 2; f++)
-                    if (r.code[f] == FPL_PASS_FILTER) {
-                        u64 a, b;
-                        Form::frag_len(g, r, f, a, b);
-                        len += a + b;
-                    }
+        if (i < n) {
+            s = it.load(i);
+            len = it.len(s);
         }
         u64 incl = gz_scan_incl_u64(len);
         if (lane_id() == 63) wsum[wave_in_block()] = incl;
         __syncthreads();
         u64 o = carry_len + incl - len;
         for (int k = 0; k < wave_in_block(); k++) o += wsum[k];
-        if (i < n_rec) rec_off[i] = o;
+        if (i < n) rec_off[i] = o;
         __syncthreads();
         if (threadIdx.x == 1023) carry_len = o + len;
-        /* the blocks that start inside this record */
+        /* the blocks that start inside this item */
         u64 cnt = 0;
-        if (i < n_rec) gz_read_cuts<Form>(g, r, o, [&](u64) { cnt++; });
+        if (i < n) it.cuts(s, o, [&](u64) { cnt++; });
         incl = gz_scan_incl_u64(cnt);
         if (lane_id() == 63) wsum[wave_in_block()] = incl;
         __syncthreads();
         u64 k0 = carry_blk + incl - cnt;
         for (int k = 0; k < wave_in_block(); k++) k0 += wsum[k];
-        if (i < n_rec) {
+        if (i < n) {
             u64 k = k0;
-            gz_read_cuts<Form>(g, r, o, [&](u64 p) {
+            it.cuts(s, o, [&](u64 p) {
                 if (k < blk_cap) blk_start[k] = p;
                 k++;
             });
@@ -310,7 +357,7 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        rec_off[n_rec] = carry_len;
+        rec_off[n] = carry_len;
         hdr->total = carry_len;
         hdr->gz_len = 0;
         hdr->crc = 0;
@@ -324,6 +371,11 @@ __device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_re
             hdr->status = 1;
         }
     }
+}
+template <class Form = GzFastqForm, class Src>
+__device__ __forceinline__ void gz_layout_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, u64* __restrict__ rec_off,
+                                               u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
+    gz_layout_scan(GzReadItem<Form, Src>{src, res}, n_rec, rec_off, blk_start, blk_cap, hdr);
 }
 
 __global__ void __launch_bounds__(1024)
@@ -408,6 +460,181 @@ k_gz_compose_bam(const u8* __restrict__ bam, const uint64_t* __restrict__ rec_st
                  const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_rec, const u64* __restrict__ rec_off,
                  u8* __restrict__ comp, u64 comp_cap) {
     gz_compose_body(GzBamSrc{bam, rec_start, seq, qual, off}, res, n_rec, rec_off, comp, comp_cap);
+}
+
+/* ---- the fragment forms (fpl_set_fragment_output): the output reads of a --break / --mask batch ----
+   The layout's lane and the compose's wave is ordered fragment j of the batch's list (frag_index.h); rec_off has an entry per
+   fragment plus one.  The bytes are format_range's with a fragment list (host/format.cpp): the name's first byte, "r<break_no>-"
+   when break_no != 0, the split prefix by kind, the rest of the name; the bases with every region of the fragment shown as N;
+   the '+' line and the qualities as they are.  A fragment whose code is not FPL_PASS_FILTER, whose read is dropped or whose
+   entry nobody claimed writes nothing. */
+struct GzFragList {
+    const fpl_fragment* frags;
+    const fpl_region* regs;
+    const u32* order;
+    const FragIndex* fi;
+};
+__device__ __forceinline__ u32 gz_break_digits(u32 break_no) { /* (16 bits: 1 - 5 digits) */
+    return break_no >= 10000 ? 5u : (break_no >= 1000 ? 4u : (break_no >= 100 ? 3u : (break_no >= 10 ? 2u : 1u)));
+}
+/* what a fragment's name line holds between the name's first byte and the rest of it: "r<i>-" and the prefix -- written whether
+   the name is empty or not, as format_range does */
+__device__ __forceinline__ u32 gz_frag_tag_len(const fpl_fragment& f, u32& pl) {
+    pl = f.kind == 1 ? 22u : (f.kind == 2 ? 23u : 0u);
+    return pl + (f.break_no ? 2u + gz_break_digits(f.break_no) : 0u);
+}
+/* ordered fragment j: its list entry, and whether it is written at all */
+__device__ __forceinline__ bool gz_frag_take(const GzFragList& fl, const fpl_read_result* __restrict__ res, u32 n_rec, u32 j, u32 n,
+                                             fpl_fragment& f) {
+    const u32 e = frag_entry(fl.order, j, n);
+    if (e == FI_NONE) return false;
+    f = fl.frags[e];
+    return f.code == FPL_PASS_FILTER && f.read < n_rec && !res[f.read].dropped;
+}
+template <class Src>
+struct GzFragItem {
+    Src src;
+    const fpl_read_result* res;
+    u32 n_rec, n;
+    GzFragList fl;
+    struct State {
+        GzRec g;
+        fpl_fragment f;
+        bool take;
+    };
+    __device__ __forceinline__ State load(u32 j) const {
+        State s = {};
+        s.take = gz_frag_take(fl, res, n_rec, j, n, s.f);
+        if (s.take) s.g = src.rec(s.f.read);
+        return s;
+    }
+    __device__ __forceinline__ void lens(const State& s, u64& a, u64& b) const {
+        u32 pl;
+        a = (u64)s.g.name_len + gz_frag_tag_len(s.f, pl) + 1 + (u64)s.f.len + 1;
+        b = (u64)s.g.strand_len + 1 + (u64)s.f.len + 1;
+    }
+    __device__ __forceinline__ u64 len(const State& s) const {
+        if (!s.take) return 0;
+        u64 a, b;
+        lens(s, a, b);
+        return a + b;
+    }
+    template <class F>
+    __device__ __forceinline__ void cuts(const State& s, u64 o, F&& emit) const {
+        if (!s.take) return;
+        u64 a, b;
+        lens(s, a, b);
+        gz_frag_cuts(o, a, b, s.f.len, emit);
+    }
+};
+/* (a status of the index is a status of the layout: bit 2, and nothing behind it runs) */
+template <class Src>
+__device__ __forceinline__ void gz_layout_frag_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, const GzFragList& fl,
+                                                    u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap,
+                                                    GzHeader* __restrict__ hdr) {
+    const u32 n = frag_index_len(fl.fi);
+    gz_layout_scan(GzFragItem<Src>{src, res, n_rec, n, fl}, n, rec_off, blk_start, blk_cap, hdr);
+    if (threadIdx.x == 0 && fl.fi->status) hdr->status |= 4u;
+}
+__global__ void __launch_bounds__(1024)
+k_gz_layout_frag(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+                 const fpl_read_result* __restrict__ res, u32 n_rec, GzFragList fl, u64* __restrict__ rec_off, u64* __restrict__ blk_start,
+                 u32 blk_cap, GzHeader* __restrict__ hdr) {
+    gz_layout_frag_body(GzTextSrc{text, line, nl_pos}, res, n_rec, fl, rec_off, blk_start, blk_cap, hdr);
+}
+__global__ void __launch_bounds__(1024)
+k_gz_layout_frag_bam(const u8* __restrict__ bam, const uint64_t* __restrict__ rec_start, const u8* __restrict__ seq, const u8* __restrict__ qual,
+                     const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_rec, GzFragList fl,
+                     u64* __restrict__ rec_off, u64* __restrict__ blk_start, u32 blk_cap, GzHeader* __restrict__ hdr) {
+    gz_layout_frag_body(GzBamSrc{bam, rec_start, seq, qual, off}, res, n_rec, fl, rec_off, blk_start, blk_cap, hdr);
+}
+
+/* len bytes of one value, the wave together */
+__device__ __forceinline__ void gz_wave_fill(u8* __restrict__ dst, u8 byte, u32 len) {
+    const u32 lane = (u32)lane_id();
+    const u32 whole = len & ~15u;
+    const u32 w = 0x01010101u * byte;
+    const u32x4 v = {w, w, w, w};
+    for (u32 i = 16 * lane; i < whole; i += 16 * 64) __builtin_memcpy(dst + i, &v, 16);
+    if (lane < (len & 15u)) dst[whole + lane] = byte;
+}
+/* the bases [start, start + len) of a read at d with the fragment's regions shown as N (frag_clip_region: append_masked's
+   clipping).  Written as DISJOINT pieces, a copy for every unmasked stretch and a fill for every region, in the regions' order
+   (ascending): a copy of the whole line with the N stored over it would have two lanes of one wave store to one byte, and
+   program order says nothing about which of the two lands last. */
+__device__ __forceinline__ void gz_wave_masked(u8* __restrict__ d, const u8* __restrict__ bases, u32 start, u32 len,
+                                               const fpl_region* __restrict__ regs, u32 n_regs) {
+    u32 pos = 0; /* bytes of the fragment written so far */
+    for (u32 k = 0; k < n_regs; k++) { /* wave-uniform */
+        u32 a, l;
+        if (!frag_clip_region(regs[k], start, len, a, l)) continue;
+        u32 e = a + l;
+        if (a < pos) a = pos; /* (the list is ascending and disjoint; one that is not still gives disjoint pieces) */
+        if (e <= a) continue;
+        if (a > pos) gz_wave_copy(d + pos, bases + start + pos, a - pos);
+        gz_wave_fill(d + a, (u8)'N', e - a);
+        pos = e;
+    }
+    if (pos < len) gz_wave_copy(d + pos, bases + start + pos, len - pos);
+}
+/* a wave per ordered fragment; comp holds hdr->total bytes */
+template <class Src>
+__device__ __forceinline__ void gz_compose_frag_body(const Src& src, const fpl_read_result* __restrict__ res, u32 n_rec, const GzFragList& fl,
+                                                     const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+    const u32 wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const u32 lane = (u32)lane_id();
+    const u32 n = frag_index_len(fl.fi);
+    for (u32 j = wave; j < n; j += n_waves) { /* wave-uniform */
+        const u64 o0 = rec_off[j], o1 = rec_off[j + 1];
+        if (o1 == o0 || o1 > comp_cap) continue;
+        fpl_fragment f;
+        if (!gz_frag_take(fl, res, n_rec, j, n, f)) continue; /* (the layout gave it bytes: it is taken) */
+        const GzRec g = src.rec_wave(f.read);
+        u8* d = comp + o0;
+        u32 pl;
+        const u32 tl = gz_frag_tag_len(f, pl);
+        if (lane == 0) {
+            u8* t = d + (g.name_len ? 1 : 0);
+            if (g.name_len) d[0] = g.lead;
+            if (f.break_no) {
+                const u32 nd = gz_break_digits(f.break_no);
+                u32 v = f.break_no;
+                t[0] = 'r';
+                for (u32 k = nd; k > 0; k--, v /= 10) t[k] = (u8)('0' + v % 10);
+                t[1 + nd] = '-';
+            }
+        }
+        if (lane < pl) {
+            const char* pf = pl == 22 ? "split-by-adapter-left-" : "split-by-adapter-right-";
+            d[(g.name_len ? 1 : 0) + (tl - pl) + lane] = (u8)pf[lane];
+        }
+        if (g.name_len > 1) gz_wave_copy(d + 1 + tl, g.name_rest, g.name_len - 1);
+        d += g.name_len + tl;
+        gz_wave_masked(d + 1, g.seq, f.start, f.len, fl.regs + f.region_first, f.region_count);
+        u8* d2 = d + 1 + f.len + 1;
+        if (g.strand) gz_wave_copy(d2, g.strand, g.strand_len); /* (wave-uniform) */
+        else if (lane == 0) d2[0] = '+';
+        u8* d3 = d2 + g.strand_len + 1;
+        gz_wave_copy(d3, g.qual + f.start, f.len);
+        if (lane == 0) {
+            d[0] = '\n';
+            d2[-1] = '\n';
+            d3[-1] = '\n';
+            d3[f.len] = '\n';
+        }
+    }
+}
+__global__ void __launch_bounds__(256)
+k_gz_compose_frag(const u8* __restrict__ text, const u32* __restrict__ line, const u32* __restrict__ nl_pos,
+                  const fpl_read_result* __restrict__ res, u32 n_rec, GzFragList fl, const u64* __restrict__ rec_off, u8* __restrict__ comp,
+                  u64 comp_cap) {
+    gz_compose_frag_body(GzTextSrc{text, line, nl_pos}, res, n_rec, fl, rec_off, comp, comp_cap);
+}
+__global__ void __launch_bounds__(256)
+k_gz_compose_frag_bam(const u8* __restrict__ bam, const uint64_t* __restrict__ rec_start, const u8* __restrict__ seq, const u8* __restrict__ qual,
+                      const uint64_t* __restrict__ off, const fpl_read_result* __restrict__ res, u32 n_rec, GzFragList fl,
+                      const u64* __restrict__ rec_off, u8* __restrict__ comp, u64 comp_cap) {
+    gz_compose_frag_body(GzBamSrc{bam, rec_start, seq, qual, off}, res, n_rec, fl, rec_off, comp, comp_cap);
 }
 
 /* ---- code lengths: the whole workgroup; everything in LDS ---- */

@@ -1,11 +1,12 @@
 /* rt_bam.h -- BAM in: records the host found (fpl_process_bam_async, fpl_decode_bam; bam_decode.h), and a BAM's BGZF blocks whose
    records the device finds itself -- a staged kind of rt_slots.h (bgzf_inflate.h, bam_walk.h) -- with the tail between two
-   submissions and the calls that bring a refused stretch back. */
+   submissions and the calls that bring a refused stretch back.  (--break / --mask: fpl_set_bam_gzip is refused until
+   fpl_set_fragment_output is on; the BGZF kind stays refused.) */
 #pragma once
 
 int fpl_set_bam_gzip(fpl_ctx* ctx, int on) {
     if (!ctx) return FPL_ERR_ARG;
-    if (on && ctx->hcfg.defer) return FPL_ERR_STATE; /* (--break / --mask write from fragment lists) */
+    if (on && ctx->hcfg.defer && !ctx->frag_out) return FPL_ERR_STATE; /* (--break / --mask write from fragment lists: fpl_set_fragment_output first) */
     ctx->bam_gzip = on != 0;
     return FPL_OK;
 }

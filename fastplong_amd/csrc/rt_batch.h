@@ -186,6 +186,57 @@ int fpl_process_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* 
     return FPL_OK;
 }
 
+/* fpl_set_fragment_output: the order of the last batch's fragment list (csrc/frag_index.h), enqueued on `st` behind the kernels
+   that wrote the list.  Sized by the list's capacity: how many fragments there are only the device knows. */
+static int frag_index(fpl_ctx* ctx, u32 n_reads, hipStream_t st) {
+    if (!ctx->d_bm_frags.ptr || !ctx->d_bm_counts.ptr) { /* (no batch has run yet) */
+        ctx->err = "fragment output: the context has no fragment list yet";
+        return FPL_ERR_STATE;
+    }
+    const size_t frag_cap = ctx->d_bm_frags.cap;
+    if (!ctx->d_fi.ptr) FPL_HIP(ctx->d_fi.alloc(1));
+    if (!ctx->d_fi_cnt.holds((size_t)n_reads + 1)) {
+        const size_t cap = grown((size_t)n_reads + 1, 1024);
+        FPL_HIP(regrow(ctx->d_fi_cnt.want(cap), ctx->d_fi_first.want(cap)));
+    }
+    if (!ctx->d_fi_order.holds(frag_cap)) FPL_HIP(regrow(ctx->d_fi_order.want(frag_cap)));
+    FPL_HIP(hipMemsetAsync(ctx->d_fi.ptr, 0, sizeof(FragIndex), st));
+    FPL_HIP(hipMemsetAsync(ctx->d_fi_cnt.ptr, 0, sizeof(u32) * ((size_t)n_reads + 1), st));
+    FPL_HIP(hipMemsetAsync(ctx->d_fi_order.ptr, 0xFF, sizeof(u32) * frag_cap, st));
+    const dim3 grid(frag_index_blocks(frag_cap, ctx->n_cu));
+    hipLaunchKernelGGL(k_frag_count, grid, dim3(FI_THREADS), 0, st, (const fpl_fragment*)ctx->d_bm_frags.ptr, (const u32*)ctx->d_bm_counts.ptr,
+                       (u32)frag_cap, n_reads, ctx->d_fi_cnt.ptr, ctx->d_fi.ptr);
+    hipLaunchKernelGGL(k_frag_first, dim3(1), dim3(FI_SCAN), 0, st, (const u32*)ctx->d_fi_cnt.ptr, n_reads, (const u32*)ctx->d_bm_counts.ptr,
+                       ctx->d_fi_first.ptr, ctx->d_fi.ptr);
+    hipLaunchKernelGGL(k_frag_place, grid, dim3(FI_THREADS), 0, st, (const fpl_fragment*)ctx->d_bm_frags.ptr, (const u32*)ctx->d_fi_cnt.ptr,
+                       (const u32*)ctx->d_fi_first.ptr, n_reads, ctx->d_fi_order.ptr, ctx->d_fi.ptr);
+    FPL_HIP(hipGetLastError());
+    return FPL_OK;
+}
+
+int fpl_set_fragment_output(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    if (!ctx->hcfg.defer) return FPL_OK; /* (without --break / --mask there is no fragment list: nothing changes) */
+    if (ctx->submitted != ctx->waited) return FPL_ERR_STATE;
+    /* the record form, tags and comments stay with the host in fragment mode: a context that has one of them on keeps it, and
+       this switch stays off */
+    if (on && (ctx->gzip_records || ctx->bam_tags || ctx->bam_comments.n != 0)) return FPL_ERR_STATE;
+    ctx->frag_out = on != 0;
+    return FPL_OK;
+}
+
+int fpl_set_emit_break_no(fpl_ctx* ctx, uint16_t* d_break_no) {
+    if (!ctx) return FPL_ERR_ARG;
+    ctx->d_emit_break_no = d_break_no;
+    return FPL_OK;
+}
+
+/* fpl_emit_batch_device with fpl_set_fragment_output: the output reads are the ordered fragments of the context's last batch */
+static int emit_fragments(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint32_t n_reads,
+                          const fpl_read_result* d_results, uint8_t* d_seq_out, uint8_t* d_qual_out, uint64_t out_cap_bytes,
+                          uint64_t* d_off_out, uint32_t out_cap_reads, uint32_t* d_src, uint8_t* d_kind, fpl_emit_info* d_info,
+                          hipStream_t stream);
+
 /* the layout's block sums grow together; the list of sources on its own (it follows the capacity the caller gives) */
 static int ensure_emit(fpl_ctx* ctx, u32 nblk, size_t n_from) {
     if (!ctx->d_emit_cnt.holds(nblk)) {
@@ -203,12 +254,15 @@ int fpl_emit_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_q
     if (!ctx || !d_info) return FPL_ERR_ARG;
     if (n_reads && (!d_seq || !d_qual || !d_off || !d_results || !d_seq_out || !d_qual_out || !d_off_out)) return FPL_ERR_ARG;
     if (n_reads > (1u << 30)) return FPL_ERR_ARG;
-    if (ctx->hcfg.defer) {
-        ctx->err = "fpl_emit_batch_device: with break_enabled / mask_enabled the output reads are the fragment list's (fpl_get_fragments)";
+    if (ctx->hcfg.defer && !ctx->frag_out) {
+        ctx->err = "fpl_emit_batch_device: with break_enabled / mask_enabled the output reads are the fragment list's (fpl_get_fragments, or fpl_set_fragment_output)";
         return FPL_ERR_STATE;
     }
     hipStream_t stream = (hipStream_t)stream_v;
     FPL_HIP(hipSetDevice(ctx->device));
+    if (ctx->hcfg.defer && n_reads)
+        return emit_fragments(ctx, d_seq, d_qual, d_off, n_reads, d_results, d_seq_out, d_qual_out, out_cap_bytes, d_off_out, out_cap_reads,
+                              d_src, d_kind, d_info, stream);
     if (!n_reads) {
         FPL_HIP(hipMemsetAsync(d_info, 0, sizeof(fpl_emit_info), stream));
         if (d_off_out) FPL_HIP(hipMemsetAsync(d_off_out, 0, sizeof(uint64_t), stream));
@@ -228,6 +282,37 @@ int fpl_emit_batch_device(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_q
     hipLaunchKernelGGL(k_emit_gather, dim3(emit_gather_blocks(out_cap_bytes, ctx->n_cu)), dim3(EM_GATHER_THREADS), 0, stream,
                        (const u8*)d_seq, (const u8*)d_qual, (const uint64_t*)d_off_out, (const EmitFrom*)ctx->d_emit_from.ptr,
                        (const fpl_emit_info*)d_info, d_seq_out, d_qual_out);
+    FPL_HIP(hipGetLastError());
+    return FPL_OK;
+}
+
+static int emit_fragments(fpl_ctx* ctx, const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint32_t n_reads,
+                          const fpl_read_result* d_results, uint8_t* d_seq_out, uint8_t* d_qual_out, uint64_t out_cap_bytes,
+                          uint64_t* d_off_out, uint32_t out_cap_reads, uint32_t* d_src, uint8_t* d_kind, fpl_emit_info* d_info,
+                          hipStream_t stream) {
+    FPL_TRY(frag_index(ctx, n_reads, stream));
+    const size_t frag_cap = ctx->d_bm_frags.cap;
+    const u32 nblk = cdiv((u32)frag_cap, (u32)EM_LAYOUT_READS); /* (a block per EM_LAYOUT_READS fragments the list has ROOM for) */
+    const size_t n_from = (size_t)std::min<uint64_t>(frag_cap, out_cap_reads);
+    FPL_TRY(ensure_emit(ctx, nblk, n_from ? n_from : 1));
+    FPL_HIP(ctx->d_emit_ent.grow(n_from ? n_from : 1, 1024));
+    const fpl_fragment* frags = ctx->d_bm_frags.ptr;
+    const u32* order = ctx->d_fi_order.ptr;
+    const FragIndex* fi = ctx->d_fi.ptr;
+    hipLaunchKernelGGL(k_emit_count_frag, dim3(nblk), dim3(EM_LAYOUT_READS), 0, stream, d_off, d_results, n_reads, frags, order, fi,
+                       ctx->d_emit_cnt.ptr, ctx->d_emit_bytes.ptr, ctx->d_emit_max.ptr);
+    hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(EM_SCAN_BLOCKS), 0, stream, ctx->d_emit_cnt.ptr, ctx->d_emit_bytes.ptr,
+                       (const u32*)ctx->d_emit_max.ptr, nblk, (u64)out_cap_bytes, out_cap_reads, d_off_out, d_info);
+    hipLaunchKernelGGL(k_emit_fill_frag, dim3(nblk), dim3(EM_LAYOUT_READS), 0, stream, d_off, d_results, n_reads, frags, order, fi,
+                       (const u32*)ctx->d_emit_cnt.ptr, (const u64*)ctx->d_emit_bytes.ptr, d_info, d_off_out, d_src, d_kind,
+                       ctx->d_emit_break_no, ctx->d_emit_from.ptr, ctx->d_emit_ent.ptr);
+    hipLaunchKernelGGL(k_emit_gather, dim3(emit_gather_blocks(out_cap_bytes, ctx->n_cu)), dim3(EM_GATHER_THREADS), 0, stream,
+                       (const u8*)d_seq, (const u8*)d_qual, (const uint64_t*)d_off_out, (const EmitFrom*)ctx->d_emit_from.ptr,
+                       (const fpl_emit_info*)d_info, d_seq_out, d_qual_out);
+    if (ctx->hcfg.msk) /* (without --mask no fragment has a region) */
+        hipLaunchKernelGGL(k_emit_mask, dim3(std::max<u32>(1u, std::min<u32>((u32)((n_from + 3) / 4), 8u * ctx->n_cu))), dim3(EM_GATHER_THREADS), 0,
+                           stream, frags, (const fpl_region*)ctx->d_bm_regs.ptr, (const u32*)ctx->d_emit_ent.ptr, (const uint64_t*)d_off_out,
+                           (const fpl_emit_info*)d_info, d_seq_out);
     FPL_HIP(hipGetLastError());
     return FPL_OK;
 }

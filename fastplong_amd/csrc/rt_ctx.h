@@ -50,6 +50,14 @@ struct fpl_ctx {
     DevBuf<u32> d_emit_cnt, d_emit_max;
     DevBuf<u64> d_emit_bytes;
     DevBuf<EmitFrom> d_emit_from;
+    /* fpl_set_fragment_output: a context with --break / --mask writes its device output forms from the fragment list of its LAST
+       batch -- one batch is in flight at a time, so the index over that list (csrc/frag_index.h) is the context's, not a slot's */
+    bool frag_out = false;
+    DevBuf<u32> d_fi_cnt, d_fi_first; /* per read: its fragments, and where they start in the order (n_reads + 1) */
+    DevBuf<u32> d_fi_order;           /* per fragment of the list's capacity: the entry at that place */
+    DevBuf<FragIndex> d_fi;
+    DevBuf<u32> d_emit_ent;           /* fpl_emit_batch_device: the list entry of every output read (k_emit_mask) */
+    uint16_t* d_emit_break_no = nullptr; /* fpl_set_emit_break_no: the caller's array, or none */
     /* The end trims of batch k + 1 beside the kernels of batch k ("trim ahead"): the trim kernel is the first of a batch, needs
        nothing of the batch before, and is bound by memory latency where k_scan / k_stats_sorted are bound by instruction issue
        -- 0.5 ms of a 12.5 ms step when two whole batches run side by side (round 4, tools/overlap_probe.py).  It writes
@@ -74,6 +82,7 @@ struct fpl_ctx {
     struct Slot {
         BatchKind kind = BatchKind::CSR;
         bool gz = false; /* a text or BAM batch whose passing reads also come back as a gzip member (`gzip` below) */
+        bool frag = false; /* ... written from the batch's fragment list (fpl_set_fragment_output on a --break / --mask context) */
         /* every kind: the reads as CSR arrays on the device (uploaded, parsed out of the text or decoded from the BAM records),
            their records there and in page-locked memory (the D2H copy never waits for a pageable destination; a text slot
            sizes h_results by the records its chunk really has) */

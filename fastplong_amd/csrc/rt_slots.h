@@ -32,6 +32,41 @@ static int ensure_slot(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n_reads, uint64_t n_
 }
 
 /* ---- gzip members of a text batch (ABI v9) and of a BAM batch (ABI v10): csrc/gz_emit.h ---- */
+/* the fragment lists of the batch as the gzip kernels take them (fpl_set_fragment_output) */
+static GzFragList gz_frag_list(const fpl_ctx* ctx) {
+    return GzFragList{ctx->d_bm_frags.ptr, ctx->d_bm_regs.ptr, ctx->d_fi_order.ptr, ctx->d_fi.ptr};
+}
+/* the layout of a --break / --mask batch: the index over its fragment list, then a lane per ordered fragment.  rec_off and the
+   block arrays are sized by the list's CAPACITY (break_mask_caps: the host knows it without a wait) */
+static int gz_layout_frag(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
+    fpl_ctx::Slot::Gzip& g = sl.gzip;
+    const bool bam = bam_records(sl.kind);
+    hipStream_t st = ctx->stream;
+    FPL_TRY(frag_index(ctx, n, st));
+    const size_t frag_cap = ctx->d_bm_frags.cap;
+    const uint64_t bases = bam ? sl.bam.bases : sl.text.bytes / 2;
+    const uint64_t blk_want = gz_frag_blocks_bound(bases, frag_cap) + 1;
+    if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
+    FPL_HIP(g.d_rec_off.grow(frag_cap + 1, 4096 / sizeof(u64)));
+    if (!g.d_blk_start.holds(blk_want)) {
+        const size_t cap = grown(blk_want, 64, 0xFFFFFFF0u);
+        FPL_HIP(regrow(g.d_blk_start.want(cap), g.d_blk_off.want(cap), g.d_blk_size.want(cap), g.d_blk_crc.want(cap)));
+    }
+    const u32 blk_cap = (u32)g.d_blk_start.cap;
+    if (bam)
+        hipLaunchKernelGGL(k_gz_layout_frag_bam, dim3(1), dim3(1024), 0, st, (const u8*)sl.bam.d_bam.ptr, (const uint64_t*)sl.bam.d_rec.ptr,
+                           (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, gz_frag_list(ctx), g.d_rec_off.ptr, g.d_blk_start.ptr, blk_cap - 1,
+                           g.d_hdr.ptr);
+    else
+        hipLaunchKernelGGL(k_gz_layout_frag, dim3(1), dim3(1024), 0, st, (const u8*)sl.text.d_text.ptr, (const u32*)sl.text.d_line.ptr,
+                           (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n, gz_frag_list(ctx), g.d_rec_off.ptr,
+                           g.d_blk_start.ptr, blk_cap - 1, g.d_hdr.ptr);
+    FPL_HIP(hipGetLastError());
+    FPL_HIP(hipMemcpyAsync(g.h_hdr.ptr, g.d_hdr.ptr, sizeof(GzHeader), hipMemcpyDeviceToHost, st));
+    FPL_HIP(hipEventRecord(g.ev, st));
+    return FPL_OK;
+}
 /* behind the per-read kernels of the batch, on their stream: where every record's output and every deflate block starts */
 static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
     fpl_ctx::Slot::Gzip& g = sl.gzip;
@@ -46,6 +81,7 @@ static int gz_layout(fpl_ctx* ctx, fpl_ctx::Slot& sl, u32 n) {
                                                 : bamout_blocks_bound(sl.text.bytes, n))
                                          : (bam ? gz_bam_blocks_bound(sl.bam.bases, n) + (notes ? bamcomment_extra_bound(sl.bam.bytes) / GZ_B + 1 : 0)
                                                 : gz_blocks_bound(sl.text.bytes, n))) + 1;
+    if (sl.frag) return gz_layout_frag(ctx, sl, n);
     if (blk_want > 0xFFFFFFF0ull) return FPL_ERR_ARG;
     FPL_HIP(g.d_rec_off.grow((size_t)n + 1, 4096 / sizeof(u64)));
     if (!g.d_blk_start.holds(blk_want)) {
@@ -160,6 +196,10 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     fpl_ctx::Slot::Gzip& g = sl.gzip;
     FPL_HIP(hipEventSynchronize(g.ev));
     const GzHeader h = *g.h_hdr.ptr;
+    if (h.status & 4u) { /* (the fragment forms: frag_index.h found the lists overflowed, or not to index) */
+        ctx->err = "break/mask lists overflowed their capacity";
+        return FPL_ERR_CAPACITY;
+    }
     if (h.status) {
         ctx->err = "gzip layout: more deflate blocks than the bound allows";
         return FPL_ERR_STATE;
@@ -172,7 +212,16 @@ static int gz_emit(fpl_ctx* ctx, fpl_ctx::Slot& sl, const uint8_t** gz, uint64_t
     FPL_HIP(g.d_out.grow(out_want + 16, 4096));
     hipStream_t st = ctx->stream;
     /* (g.records: the bytes are BAM records, csrc/bam_emit.h; the block kernels below do not care) */
-    if (g.tags && g.moves && g.records && bam_records(sl.kind))
+    if (sl.frag && bam_records(sl.kind))
+        hipLaunchKernelGGL(k_gz_compose_frag_bam, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
+                           (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
+                           (const fpl_read_result*)sl.d_results.ptr, n, gz_frag_list(ctx), (const u64*)g.d_rec_off.ptr, g.d_comp.ptr,
+                           (u64)h.total);
+    else if (sl.frag)
+        hipLaunchKernelGGL(k_gz_compose_frag, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.text.d_text.ptr,
+                           (const u32*)sl.text.d_line.ptr, (const u32*)sl.text.d_nl.ptr, (const fpl_read_result*)sl.d_results.ptr, n,
+                           gz_frag_list(ctx), (const u64*)g.d_rec_off.ptr, g.d_comp.ptr, (u64)h.total);
+    else if (g.tags && g.moves && g.records && bam_records(sl.kind))
         hipLaunchKernelGGL(k_bamout_compose_bam_moves, dim3(8 * ctx->n_cu), dim3(256), 0, st, (const u8*)sl.bam.d_bam.ptr,
                            (const uint64_t*)sl.bam.d_rec.ptr, (const u8*)sl.d_seq.ptr, (const u8*)sl.d_qual.ptr, (const uint64_t*)sl.d_off.ptr,
                            (const fpl_read_result*)sl.d_results.ptr, n, (const BamTagInfo*)g.d_tag_info.ptr,
@@ -285,16 +334,20 @@ static inline bool read_len_ok(const uint64_t* off, u32 i, u32& max_len) {
 /* ---- the slot protocol ---- */
 /* A submission, behind its own argument checks: room in the queue, the device, --break / --mask (the fragment lists of the batch
    in flight live in buffers the next batch's kernels reuse, and they are read batch by batch: a CSR or BAM batch is let in while
-   nothing is in flight, a staged kind never); then the next slot, reset for `kind`.  Nothing counts before slot_commit. */
+   nothing is in flight, a text batch under the same rule once fpl_set_fragment_output is on, the resident kinds never); then the next slot, reset for `kind`.  Nothing counts before slot_commit. */
 static int slot_begin(fpl_ctx* ctx, BatchKind kind, bool gz, fpl_ctx::Slot*& out) {
     if (ctx->submitted - ctx->waited >= FPL_MAX_IN_FLIGHT) return FPL_ERR_STATE;
     FPL_HIP(hipSetDevice(ctx->device));
     const bool staged = staged_kind(kind);
-    if (ctx->hcfg.defer && (staged || ctx->submitted != ctx->waited)) return FPL_ERR_STATE;
+    /* (fpl_set_fragment_output lets a text batch in under the rule of the CSR and BAM kinds: the lists are sized in its stage 2,
+       once the parse has said how many reads there are -- fpl_process_batch_device.  The resident kinds stay out.) */
+    const bool refused = staged && !(ctx->frag_out && kind == BatchKind::Text);
+    if (ctx->hcfg.defer && (refused || ctx->submitted != ctx->waited)) return FPL_ERR_STATE;
     /* (the slot's previous batch has been waited for -- FPL_MAX_IN_FLIGHT slots, FIFO -- so its buffers are free) */
     fpl_ctx::Slot& sl = ctx->slot[ctx->submitted % FPL_MAX_IN_FLIGHT];
     sl.kind = kind;
     sl.gz = gz;
+    sl.frag = ctx->hcfg.defer && ctx->frag_out;
     sl.gzip.records = ctx->gzip_records;
     sl.gzip.tags = ctx->bam_tags;
     sl.gzip.mods = ctx->bam_tags && ctx->bam_mods;

@@ -120,12 +120,14 @@ int fpl_set_gzip_framing(fpl_ctx* ctx, int framing) {
 
 int fpl_set_gzip_records(fpl_ctx* ctx, int records) {
     if (!ctx || (records != FPL_GZIP_FASTQ && records != FPL_GZIP_BAM)) return FPL_ERR_ARG;
+    if (records == FPL_GZIP_BAM && ctx->hcfg.defer && ctx->frag_out) return FPL_ERR_STATE; /* (the record form stays with the host in fragment mode) */
     ctx->gzip_records = records == FPL_GZIP_BAM; /* (read by slot_begin, like the framing) */
     return FPL_OK;
 }
 
 int fpl_set_bam_tags(fpl_ctx* ctx, int on) {
     if (!ctx) return FPL_ERR_ARG;
+    if (on && ctx->hcfg.defer && ctx->frag_out) return FPL_ERR_STATE; /* (as the record form) */
     ctx->bam_tags = on != 0; /* (read by slot_begin, like the framing; a slot that holds no BAM records ignores it) */
     return FPL_OK;
 }
@@ -140,6 +142,7 @@ int fpl_set_bam_comments(fpl_ctx* ctx, const char* tags, int n_tags) {
     if (!ctx || (n_tags > 0 && !tags)) return FPL_ERR_ARG;
     bamcomment::Selection s;
     if (!bamcomment::make_selection(tags, n_tags, s)) return FPL_ERR_ARG;
+    if (s.n != 0 && ctx->hcfg.defer && ctx->frag_out) return FPL_ERR_STATE; /* (as the record form) */
     ctx->bam_comments = s; /* (read by slot_begin, like the framing; a slot whose gzip bytes are not the FASTQ text of BAM records ignores it) */
     return FPL_OK;
 }

@@ -30,7 +30,7 @@ EXPORTS = [
     "fpl_set_bam_moves", "fpl_get_bam_move_stats",
     "fpl_set_bam_comments", "fpl_get_bam_comment_stats",
     "fpl_inflater_create", "fpl_inflate_bgzf", "fpl_inflater_destroy", "fpl_inflate_gzip",
-    "fpl_emit_batch_device",
+    "fpl_emit_batch_device", "fpl_set_fragment_output", "fpl_set_emit_break_no",
     "fpl_process_bgzf_bam_async", "fpl_peek_bgzf_bam", "fpl_start_bgzf_bam", "fpl_wait_bgzf_bam", "fpl_bam_tail_get", "fpl_bam_tail_set",
     "fpl_resume_bgzf_bam", "fpl_reserve_bam_tail",
     "fpl_process_bgzf_text_async", "fpl_peek_bgzf_text", "fpl_start_bgzf_text", "fpl_wait_bgzf_text",
@@ -199,6 +199,11 @@ def load_library(path=None):
         L.fpl_emit_batch_device.restype = C.c_int
         L.fpl_emit_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "fpl_set_fragment_output"):  # (found by name: without it Engine.set_fragment_output raises)
+        L.fpl_set_fragment_output.restype = C.c_int
+        L.fpl_set_fragment_output.argtypes = [C.c_void_p, C.c_int]
+        L.fpl_set_emit_break_no.restype = C.c_int
+        L.fpl_set_emit_break_no.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "fpl_process_bgzf_bam_async"):  # (found by name too: without them Engine.submit_bgzf raises)
         L.fpl_process_bgzf_bam_async.restype = C.c_int
         L.fpl_process_bgzf_bam_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64]
@@ -656,7 +661,10 @@ class Engine:
         qual_out (uint8, equally long), off_out (int64, reads + 1), src (int32) and kind (uint8) with a slot per read off_out
         has room for.  Asynchronous on `stream` (default: torch's current stream) and without a synchronize: the tensors hold
         the batch once the stream has got there, info_t (32 bytes, uint8; emit_info reads it back) says how much of them it
-        fills.  Behind a process_device on the same stream the two calls need nothing between them."""
+        fills.  Behind a process_device on the same stream the two calls need nothing between them.
+        After set_fragment_output(True) on a --break / --mask engine the output reads are the passing fragments of the LAST
+        process_device: off_out defaults to the room their number's bound asks for, the bases carry their N, and
+        self.emit_break_no (int16, a slot per read off_out has room for) holds break_no of every output read."""
         import torch
 
         if not hasattr(self.L, "fpl_emit_batch_device"):
@@ -667,9 +675,17 @@ class Engine:
             seq_out = torch.empty(max(seq_t.numel(), 1), dtype=torch.uint8, device=dev)
         if qual_out is None:
             qual_out = torch.empty(seq_out.numel(), dtype=torch.uint8, device=dev)
+        frag_out = getattr(self, "_frag_out", False)
         if off_out is None:
-            off_out = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)
+            most = 2 * n
+            if frag_out:  # (break_mask_caps, csrc/pipeline.h: every further fragment costs a break window and a base)
+                w = int(self.opt.break_window) if self.opt.break_enabled and self.opt.break_window > 0 else 1 << 62
+                most = 2 * n + seq_t.numel() // (w + 1) + 16
+            off_out = torch.empty(most + 1, dtype=torch.int64, device=dev)
         cap_reads = off_out.numel() - 1
+        if frag_out:
+            self.emit_break_no = torch.empty(max(cap_reads, 1), dtype=torch.int16, device=dev)
+            self._check(self.L.fpl_set_emit_break_no(self.h, self.emit_break_no.data_ptr()), "fpl_set_emit_break_no")
         if src is None:
             src = torch.empty(max(cap_reads, 1), dtype=torch.int32, device=dev)
         if kind is None:
@@ -750,6 +766,15 @@ class Engine:
         if not hasattr(self.L, "fpl_set_gzip_framing"):
             raise FplError("the loaded libfastplong_amd.so has no fpl_set_gzip_framing")
         self._check(self.L.fpl_set_gzip_framing(self.h, abi.FPL_GZIP_BGZF if bgzf else abi.FPL_GZIP_MEMBER), "fpl_set_gzip_framing")
+
+    def set_fragment_output(self, on):
+        """fpl_set_fragment_output: a context with break_enabled / mask_enabled writes its device output forms -- submit_text /
+        submit_bam with gzip=True, emit_device -- from the fragment list of its last batch, ordered on the device.  Without
+        the two options the call changes nothing."""
+        if not hasattr(self.L, "fpl_set_fragment_output"):
+            raise FplError("the loaded libfastplong_amd.so has no fpl_set_fragment_output")
+        self._check(self.L.fpl_set_fragment_output(self.h, int(bool(on))), "fpl_set_fragment_output")
+        self._frag_out = bool(on) and bool(self.opt.break_enabled or self.opt.mask_enabled)
 
     def set_gzip_records(self, bam):
         """fpl_set_gzip_records: the gzip batches submitted from now on are unaligned BAM records in BGZF blocks (True; a file is

@@ -54,6 +54,9 @@ struct DeviceApi {
     typedef int (*SetBamCommentsFn)(fpl_ctx*, const char*, int);
     SetBamCommentsFn set_bam_comments = nullptr;
     BamTagStatsFn get_bam_comment_stats = nullptr;
+    /* --break / --mask with --device_gzip: the device writes its gzip batches from the fragment lists (found by name; without it
+       such a run stays with the host's formatter) */
+    SetGzipFn set_fragment_output = nullptr;
 };
 
 static DeviceApi load_device_api() {
@@ -78,7 +81,16 @@ static DeviceApi load_device_api() {
     a.get_bam_move_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_move_stats");
     a.set_bam_comments = (DeviceApi::SetBamCommentsFn)dlsym(RTLD_DEFAULT, "fpl_set_bam_comments");
     a.get_bam_comment_stats = (DeviceApi::BamTagStatsFn)dlsym(RTLD_DEFAULT, "fpl_get_bam_comment_stats");
+    a.set_fragment_output = (DeviceApi::SetGzipFn)dlsym(RTLD_DEFAULT, "fpl_set_fragment_output");
     return a;
+}
+
+/* --break / --mask: may the device write this run's --out?  Only when --device_gzip asks for it, under the other conditions of
+   the device's gzip form (a .gz, no --split*, -z <= 4, no --host_gzip, not BAM records, no --comment_tags) and with a library
+   that has the call.  Without the flag nothing about such a run changes. */
+static bool fragment_device_out(const Options& opt, const DeviceApi& api) {
+    return opt.fragmentMode && opt.deviceGzip && api.set_fragment_output && ends_with_gz(opt.out) && !opt.toStdout && !opt.splitEnabled &&
+           opt.compression <= 4 && !opt.hostGzip && !opt.commentTags;
 }
 
 /* BGZF framing (set_gzip_framing) or BAM records (set_gzip_records: FPL_GZIP_BAM is 1 like FPL_GZIP_BGZF) on every context or

@@ -222,12 +222,14 @@ static InputPlan plan_input(const Options& opt, const InputFacts& in, const Devi
     p.nWork = (p.chunked ? p.readerThreads : 1) + (FPL_MAX_IN_FLIGHT + 1) * opt.nGpus + 2 + (gzOut ? 3 : 0) + (p.chunked ? max(0, extraWork) : 0);
     /* --device_parse: the chunk parsers only LOAD the file's bytes (page-locked), the device finds the records
        (fpl_process_text_async); --break / --mask keep the host's reader (their fragment lists come back batch by batch through
-       the CSR entry points), and so do inputs that are not cut into chunks (pipes, a streamed gzip, a small file) */
+       the CSR entry points) unless --device_gzip has the device write their output, and so do inputs that are not cut into chunks (pipes, a streamed gzip, a small file) */
     /* (the default wherever it applies; --host_parse keeps the host's parsers, --device_parse only says so out loud) */
     if (opt.deviceParse && opt.hostParse) error_exit("--device_parse and --host_parse exclude each other");
-    p.textMode = !opt.hostParse && !getenv("FPLH_HOST_PARSE") && p.chunked && !opt.fragmentMode && p.chunkBytes < (3ull << 30);
+    /* (--break / --mask with --device_gzip, where the device may write the output: fpl_set_fragment_output lets text batches in) */
+    p.textMode = !opt.hostParse && !getenv("FPLH_HOST_PARSE") && p.chunked && (!opt.fragmentMode || fragment_device_out(opt, api)) &&
+                 p.chunkBytes < (3ull << 30);
     if (opt.deviceParse && !p.textMode && opt.verbose)
-        cerr << "input: --device_parse does not apply (it needs an uncompressed file or multi-member gzip cut into chunks, --chunk_mb below 3072, no --break / --mask): the host parses" << endl;
+        cerr << "input: --device_parse does not apply (it needs an uncompressed file or multi-member gzip cut into chunks, --chunk_mb below 3072, --break / --mask only with --device_gzip and a .gz output): the host parses" << endl;
     if (p.chunked && p.textMode) /* one block holds a chunk's text and the stretch behind it that the last record may run into */
         fplh::ByteBuf::set_arena((size_t)(p.chunkBytes + (5u << 20)), (size_t)p.nWork);
     else if (p.chunked) /* a chunk holds about half its bytes in bases: one block each for the bases and the qualities of a batch */

@@ -280,10 +280,17 @@ Pipeline::Pipeline(const Options& opt_, const DeviceApi& api_, const InputFacts&
    fpl_wait_text_gz, C-ABI version 9) and the writer appends the member; a chunk that falls back to the host's reader, and a
    batch the library makes no member for, is formatted and deflated here as before -- members are self-contained, so the
    two kinds mix in one file.  -z 5..9 ask for a smaller file than a Huffman-only coder gives and keep the host's deflate;
-   so do --failed_out's own file, --split*, --break / --mask (never text batches), --host_parse, --host_gzip.
+   so do --failed_out's own file, --split*, --break / --mask without --device_gzip, --host_parse, --host_gzip.
    A library without the entry points (DeviceApi): the host's deflate, without a word. */
 void Pipeline::enable_device_gzip() {
-    bool eligible = out.fout && out.fout.gz && !out.split && !opt.fragmentMode && !opt.hostGzip && opt.compression <= 4;
+    bool eligible = out.fout && out.fout.gz && !out.split && !opt.hostGzip && opt.compression <= 4;
+    /* --break / --mask: only with --device_gzip, FASTQ text only, and only where every context takes fpl_set_fragment_output (the
+       device then composes from the fragment lists; the host still fetches them for the reports and --failed_out) */
+    if (opt.fragmentMode) {
+        const bool on = eligible && fragment_device_out(opt, api) && !out.fout.bam && enable_on_all(api.set_fragment_output, true, ctxs);
+        if (!on && in.textMode) error_exit("--break / --mask: the device cannot write this output (fpl_set_fragment_output refused)");
+        eligible = on;
+    }
     /* --bgzf: under the same conditions the device frames its batches as BGZF blocks; a library without fpl_set_gzip_framing
        makes members only, so the host deflates and frames everything, without a word */
     /* --out *.bam: the device form under the conditions of a .gz output WITH --device_gzip, for text batches and BAM-backed ones
@@ -467,6 +474,7 @@ class DeviceStage {
     bool approve_next();
     void finish_oldest();
     void finish_csr(Work* w);
+    void fetch_fragments(Work* w);
     void finish_text(Work* w, int state);
     Work* take();
     void submit(Work* w);
@@ -559,17 +567,20 @@ void DeviceStage::finish_csr(Work* w) {
         else if (gzn) take_member(w, gzp, gzn);
         else if (member) w->dev_gz_empty = true; /* no member: nothing of this batch passed */
     }
-    if (w->rc == FPL_OK && fragmentMode) { /* any number of output reads per read: fetch the list */
-        uint32_t nf = 0, nr = 0;
-        int rc = fpl_fragment_counts(ctx, &nf, &nr);
-        if (rc == FPL_OK) {
-            w->frags.frags.resize(nf);
-            w->frags.regs.resize(nr);
-            rc = fpl_get_fragments(ctx, w->frags.frags.data(), nf, w->frags.regs.data(), nr);
-            w->frags.index(w->batch.n());
-        }
-        if (rc != FPL_OK) fail(w, rc);
+    if (w->rc == FPL_OK && fragmentMode) fetch_fragments(w);
+}
+
+/* --break / --mask, any number of output reads per read: the list of the batch just waited for */
+void DeviceStage::fetch_fragments(Work* w) {
+    uint32_t nf = 0, nr = 0;
+    int rc = fpl_fragment_counts(ctx, &nf, &nr);
+    if (rc == FPL_OK) {
+        w->frags.frags.resize(nf);
+        w->frags.regs.resize(nr);
+        rc = fpl_get_fragments(ctx, w->frags.frags.data(), nf, w->frags.regs.data(), nr);
+        w->frags.index(w->batch.n());
     }
+    if (rc != FPL_OK) fail(w, rc);
 }
 
 /* (a slot that was cancelled -- dropped, or handed back with w == nullptr -- is waited for all the same: the library's
@@ -589,6 +600,7 @@ void DeviceStage::finish_text(Work* w, int state) {
             w->batch.adopt_lines(ls, tr.n_reads);
             p.nTextBatches++;
             if (gzn) take_member(w, gzp, gzn); /* (no member: nothing passed, or the library makes none -- the formatter's turn) */
+            if (fragmentMode) fetch_fragments(w); /* (the reports and --failed_out work from the list) */
         }
     } else if (w && rc != FPL_OK && w->rc == FPL_OK) {
         fail(w, rc);

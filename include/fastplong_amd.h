@@ -420,7 +420,7 @@ int fpl_decode_bam(int32_t device, const uint8_t* bam, uint64_t n_bytes, const u
  *                      counters.  A gzip batch may pass seq_out == NULL && qual_out == NULL: the decoded arrays are then not
  *                      copied back.  Both NULL or neither (FPL_ERR_ARG otherwise); with the switch off NULL stays FPL_ERR_ARG.
  *                      Contexts with break_enabled / mask_enabled write from fragment lists: the switch is refused
- *                      (FPL_ERR_STATE) for them.
+ *                      (FPL_ERR_STATE) for them until fpl_set_fragment_output is on.
  *   fpl_wait_bam_gz    fpl_wait for the oldest batch in flight, plus its bytes: one complete gzip member whose inflation is, byte
  *                      for byte, what the host's formatter appends to --out for the batch's FASTQ twin and `results` -- name
  *                      line '@' + the record's read name (up to its NUL), the '+' line the one byte '+', and as for
@@ -864,7 +864,8 @@ int fpl_inflate_gzip(fpl_inflater* inf, const uint8_t* comp, uint64_t comp_bytes
  * per output read -- grows like every other: rarely, with headroom, behind a device-wide wait).  Placed on the stream behind the
  * fpl_process_batch_device that writes d_results, it is ordered behind it.  n_reads == 0 gives an all-zero info.
  * FPL_ERR_ARG: ctx or d_info NULL, n_reads > 0 with any other pointer but d_src / d_kind NULL, n_reads > 2^30.  FPL_ERR_STATE:
- * a context with break_enabled / mask_enabled -- its reads live in the fragment list (fpl_get_fragments), not in the records.
+ * a context with break_enabled / mask_enabled -- its reads live in the fragment list (fpl_get_fragments), not in the records --
+ * unless fpl_set_fragment_output is on (below: the call then puts out the fragments).  status bit 2 is that form's.
  */
 typedef struct fpl_emit_info { /* 32 bytes, written in DEVICE memory */
     uint64_t n_bytes;          /* bytes of d_seq_out / d_qual_out used = d_off_out[n_out] */
@@ -892,6 +893,44 @@ void fpl_host_free(void* p);
 int fpl_fragment_counts(fpl_ctx* ctx, uint32_t* n_fragments, uint32_t* n_regions);
 int fpl_get_fragments(fpl_ctx* ctx, fpl_fragment* fragments, uint32_t n_fragments, fpl_region* regions,
                       uint32_t n_regions);
+
+/*
+ * Device output for contexts with break_enabled / mask_enabled, from the fragment list.  FPL_ABI_VERSION stays 10: found by symbol
+ * lookup like fpl_set_gzip_framing; a caller of a library without it formats such runs on the host, as before.
+ *
+ * Without the switch every device output form refuses such a context (fpl_set_bam_gzip, fpl_emit_batch_device, text batches), and
+ * nothing here changes that.  With it the fragment list of the LAST batch is put in the reference's order on the device
+ * (csrc/frag_index.h: place = first[read] + seq_no, no sort) and read there:
+ *
+ *   fpl_set_fragment_output  per context, while nothing is in flight (FPL_ERR_STATE otherwise).  On a context without
+ *                      break_enabled / mask_enabled it succeeds and changes nothing.  While it is on
+ *                        - fpl_set_bam_gzip succeeds, and fpl_wait_bam_gz returns the member of the batch's FRAGMENTS;
+ *                        - fpl_process_text_async is admitted under the rule CSR and BAM batches have -- nothing else in flight
+ *                          --, with fpl_set_text_gzip its member is the fragments' too.  The resident kinds
+ *                          (fpl_process_bgzf_bam_async, fpl_process_bgzf_text_async) stay FPL_ERR_STATE;
+ *                        - fpl_emit_batch_device puts out the fragments (below);
+ *                        - fpl_set_gzip_records(FPL_GZIP_BAM), fpl_set_bam_tags(1) and fpl_set_bam_comments with a selection
+ *                          are FPL_ERR_STATE, and the switch itself is FPL_ERR_STATE while one of them is on: those forms
+ *                          stay with the host in fragment mode.
+ *   The member (or the BGZF blocks, fpl_set_gzip_framing) inflates to exactly what the host's formatter writes for the batch and
+ *   its fragment list (host/format.cpp, format_range with a FragmentList): per fragment with code FPL_PASS_FILTER of a read that
+ *   is not dropped, in (read, seq_no) order, the name's first byte, "r<break_no>-" when break_no != 0, the split prefix by kind,
+ *   the rest of the name; the bases with the fragment's regions as 'N'; the '+' line and the qualities unmasked.  Sizes as for
+ *   the other gzip batches, with `fragments` the list's.  A list that overflowed (fpl_fragment_counts: FPL_ERR_CAPACITY) makes
+ *   the wait FPL_ERR_CAPACITY and nothing is written.
+ *
+ *   fpl_emit_batch_device with the switch on: the output reads are the passing fragments of the context's LAST batch -- the lists
+ *   fpl_get_fragments reads, valid until the context's next fpl_process_batch_device --, so the call belongs behind that batch
+ *   on its stream, with the batch's d_seq / d_qual / d_off / n_reads.  Of d_results only `dropped` is read.  d_src[j] is the read,
+ *   d_kind[j] the fragment's kind; the bases carry their 'N' (k_emit_mask runs behind the gather), the qualities do not.
+ *   out_cap_reads = the fragment count's bound (2 * n_reads + bases / (break window + 1) + 16) and out_cap_bytes = d_off[n_reads]
+ *   always suffice.  fpl_emit_info.status bit 2: the lists overflowed or do not index; n_out = 0 and nothing else is written.
+ *   fpl_set_emit_break_no  a DEVICE array of out_cap_reads uint16 the next fpl_emit_batch_device calls fill with break_no of
+ *                      every output read (with d_src and d_kind: what names it); NULL (the default): none.  Read only with the
+ *                      switch on.
+ */
+int fpl_set_fragment_output(fpl_ctx* ctx, int on);
+int fpl_set_emit_break_no(fpl_ctx* ctx, uint16_t* d_break_no);
 
 /* Counter buffer: capacity, number of adapter slots, length, device pointer, host copy. */
 uint32_t fpl_max_cycles(const fpl_ctx* ctx);

@@ -324,6 +324,12 @@ int fpl_get_bam_comment_stats(fpl_ctx* ctx, uint64_t* out) {
     for (int k = 0; k < 4; k++) out[k] = 0;
     return FPL_OK;
 }
+/* (nor composes from fragment lists: a --break / --mask run keeps the host's formatter) */
+int fpl_set_fragment_output(fpl_ctx* ctx, int on) {
+    if (!ctx) return FPL_ERR_ARG;
+    return on ? FPL_ERR_NO_DEVICE : FPL_OK;
+}
+int fpl_set_emit_break_no(fpl_ctx* ctx, uint16_t*) { return ctx ? FPL_OK : FPL_ERR_ARG; }
 /* (nor mv and ts: the host writes every record of a --keep_moves run) */
 int fpl_set_bam_moves(fpl_ctx* ctx, int on) {
     if (!ctx) return FPL_ERR_ARG;
