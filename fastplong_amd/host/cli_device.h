@@ -86,11 +86,11 @@ static DeviceApi load_device_api() {
 }
 
 /* --break / --mask: may the device write this run's --out?  Only when --device_gzip asks for it, under the other conditions of
-   the device's gzip form (a .gz, no --split*, -z <= 4, no --host_gzip, not BAM records, no --comment_tags) and with a library
+   the device's gzip form (a .gz, no --split*, -z <= 4, no --host_gzip, not BAM records, no --comment_tags, no --reindex_comments) and with a library
    that has the call.  Without the flag nothing about such a run changes. */
 static bool fragment_device_out(const Options& opt, const DeviceApi& api) {
     return opt.fragmentMode && opt.deviceGzip && api.set_fragment_output && ends_with_gz(opt.out) && !opt.toStdout && !opt.splitEnabled &&
-           opt.compression <= 4 && !opt.hostGzip && !opt.commentTags;
+           opt.compression <= 4 && !opt.hostGzip && !opt.commentTags && !opt.reindexComments;
 }
 
 /* BGZF framing (set_gzip_framing) or BAM records (set_gzip_records: FPL_GZIP_BAM is 1 like FPL_GZIP_BGZF) on every context or

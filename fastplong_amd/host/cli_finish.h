@@ -77,6 +77,12 @@ static void print_pipeline_summary(const Pipeline& p) {
         }
         cerr << "FASTQ comments: " << t[0] << " records, " << t[1] << " fields, " << t[2] << " bytes, " << t[3] << " fields left out (control bytes)" << endl;
     }
+    if (p.opt.reindexComments) {
+        uint64_t t[5];
+        for (int k = 0; k < 5; k++) t[k] = g_fqCommentStats[k].load();
+        cerr << "FASTQ comments re-indexed: " << t[0] << " reads, " << t[1] << " not re-indexable and dropped, " << t[2] << " positions kept, " << t[3]
+             << " cut away, " << t[4] << " reads left as they are (not tags)" << endl;
+    }
     if (in.textMode)
         cerr << "device parse: " << p.nTextBatches.load() << " chunks parsed on the device, " << p.nTextFallbacks.load()
              << " handed back to the host's reader (irregular text)" << endl;

@@ -28,6 +28,7 @@ static InputFacts evaluate_input(Options& opt, const DeviceApi& api) {
     in.bam = !opt.from_stdin && fplh::is_bam_file(opt.in);
     if (opt.keepTags && !in.bam) error_exit("--keep_tags needs BAM input (--in " + opt.in + " is not a BAM file)");
     if (opt.commentTags && !in.bam) error_exit("--comment_tags needs BAM input (--in " + opt.in + " is not a BAM file)");
+    if (opt.reindexComments && in.bam) error_exit("--reindex_comments needs FASTQ input (--in " + opt.in + " is a BAM file: --comment_tags writes its fields as comments, re-indexed)");
     if (in.bam) {
         const DeviceApi::BamDecodeFn bamDecode = api.decode_bam;
         if (!api.process_bam_async || !bamDecode)

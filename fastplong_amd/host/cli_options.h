@@ -82,7 +82,7 @@ static const Flag FLAGS[] = {
     {"report_title", 'R', true, "fastplong report"}, {"thread", 'w', true, "3"}, {"split", 0, true, "0"},
     {"split_by_lines", 0, true, "0"}, {"split_prefix_digits", 0, true, "4"},
     {"gpus", 0, true, "1"}, {"batch_mbases", 0, true, "256"}, {"batch_reads", 0, true, "0"},
-    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""}, {"keep_moves", 0, false, ""}, {"comment_tags", 0, true, ""},
+    {"reader_threads", 0, true, "0"}, {"chunk_mb", 0, true, "32"}, {"gz_stream", 0, false, ""}, {"device_parse", 0, false, ""}, {"host_parse", 0, false, ""}, {"host_gzip", 0, false, ""}, {"device_gzip", 0, false, ""}, {"device_inflate", 0, false, ""}, {"bgzf", 0, false, ""}, {"keep_tags", 0, false, ""}, {"keep_mods", 0, false, ""}, {"keep_moves", 0, false, ""}, {"comment_tags", 0, true, ""}, {"reindex_comments", 0, false, ""},
 };
 
 struct Args {
@@ -178,6 +178,9 @@ struct Options {
     /* --comment_tags LIST: BAM input's auxiliary fields go behind the name lines of every FASTQ output (README "Tags as FASTQ comments") */
     bool commentTags = false;
     fplh::BamCommentSelection commentSel = {};
+    /* --reindex_comments: the SAM fields a FASTQ input carries as comments follow every trim and split into the FASTQ outputs (README
+       "Comments of a FASTQ input"; csrc/fq_comment_rules.h) */
+    bool reindexComments = false;
     string command; /* src/main.cpp:252-256 */
     time_t t1 = 0;
 };
@@ -241,6 +244,11 @@ static void validate(const Args& cmd, Options& p, int wShared, int qShared) {
     }
     if (o.ed_max < 0 || o.ed_max > 1.0) error_exit("the adapter <distance_threshold> should be 0.0 ~ 1.0, suggest 0.1 ~ 0.3");
     if (o.trimming_extension < 0 || o.trimming_extension > 100) error_exit("the adapter <trimming_extension> should be 0 ~ 100, suggest 5 ~ 30");
+}
+
+/* the run writes FASTQ text somewhere: --stdout, an --out (or its --split* files) or a --failed_out that is not a .bam */
+static bool has_fastq_output(const Options& p) {
+    return p.toStdout || (!p.out.empty() && !ends_with_bam(p.out)) || (!p.splitEnabled && !p.failedOut.empty() && !ends_with_bam(p.failedOut));
 }
 
 static Options parse_options(int argc, char** argv) {
@@ -347,8 +355,12 @@ static Options parse_options(int argc, char** argv) {
     if (p.commentTags) {
         if (!fplh::parse_comment_tags(cmd.str("comment_tags"), p.commentSel))
             error_exit("--comment_tags takes * or a list of 1 to 32 two-character tags such as MM,ML (got: " + cmd.str("comment_tags") + ")");
-        const bool fastqOut = p.toStdout || (!p.out.empty() && !ends_with_bam(p.out)) || (!p.splitEnabled && !p.failedOut.empty() && !ends_with_bam(p.failedOut));
-        if (!fastqOut) error_exit("--comment_tags needs a FASTQ output (--out, --failed_out, --stdout or the --split files; a .bam output follows --keep_tags)");
+        if (!has_fastq_output(p)) error_exit("--comment_tags needs a FASTQ output (--out, --failed_out, --stdout or the --split files; a .bam output follows --keep_tags)");
+    }
+    p.reindexComments = cmd.exist("reindex_comments");
+    if (p.reindexComments) {
+        if (p.commentTags) error_exit("--reindex_comments and --comment_tags exclude each other (the one is for FASTQ input, the other for BAM input)");
+        if (!has_fastq_output(p)) error_exit("--reindex_comments needs a FASTQ output (--out, --failed_out, --stdout or the --split files; a .bam output cuts its names at the first tab)");
     }
     if (p.splitEnabled && ends_with_bam(p.out)) error_exit("--split / --split_by_lines do not write BAM files (--out " + p.out + ")");
 

@@ -26,6 +26,7 @@ struct Work {
     fplh::FragmentList frags; /* --break / --mask */
     vector<string> outs, faileds;
     vector<fplh::BamTagSrc> outTags, failedTags; /* --keep_tags: where the records of outs / faileds take their auxiliary fields from */
+    vector<fplh::FqCommentSrc> outNotes, failedNotes; /* --reindex_comments: which input read and range every record of outs / faileds is */
     string gz_member;  /* --out *.gz deflated on the device (fpl_wait_text_gz): this batch's gzip member, written as it is */
     bool dev_gz = false;
     bool dev_gz_empty = false; /* a gzip BAM batch in which nothing passed: --out gets nothing, and the decoded arrays may never have come back */
@@ -284,6 +285,10 @@ Pipeline::Pipeline(const Options& opt_, const DeviceApi& api_, const InputFacts&
    A library without the entry points (DeviceApi): the host's deflate, without a word. */
 void Pipeline::enable_device_gzip() {
     bool eligible = out.fout && out.fout.gz && !out.split && !opt.hostGzip && opt.compression <= 4;
+    /* --reindex_comments: the name lines of FASTQ text are the host's to rewrite -- there is no device form of the flag --, so the
+       host formats and deflates every batch of such a run, with or without --device_gzip.  (A .bam output cuts its names at the
+       first tab and stays as it is.) */
+    if (opt.reindexComments && !(out.fout && out.fout.bam)) eligible = false;
     /* --break / --mask: only with --device_gzip, FASTQ text only, and only where every context takes fpl_set_fragment_output (the
        device then composes from the fragment lists; the host still fetches them for the reports and --failed_out) */
     if (opt.fragmentMode) {
@@ -738,6 +743,11 @@ void Pipeline::format_stage(int f) {
             const bool noteFailed = out.comments && w->batch.bam_backed && toFailed && !out.ffail.bam;
             if (noteOut) w->outTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outTags, true), out.comment_pieces(w->outs, w->outTags);
             if (noteFailed) w->failedTags.clear(), fplh::bam_tag_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedTags, true), out.comment_pieces(w->faileds, w->failedTags);
+            /* --reindex_comments: a text input's comments follow the trims and splits, for the same outputs, in the same place */
+            const bool fixOut = out.reindexComments && !w->batch.bam_backed && out.fout && !out.fout.bam && !w->dev_gz;
+            const bool fixFailed = out.reindexComments && !w->batch.bam_backed && toFailed && !out.ffail.bam;
+            if (fixOut) w->outNotes.clear(), fplh::fq_comment_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, false, w->outNotes), out.reindex_pieces(w->outs, w->outNotes);
+            if (fixFailed) w->failedNotes.clear(), fplh::fq_comment_sources(w->batch, w->res.data(), 0, w->batch.n(), fl, true, w->failedNotes), out.reindex_pieces(w->faileds, w->failedNotes);
             if (w->dev_gz) { /* (formatted for --failed_out alone) */
                 w->outs.resize(1);
                 w->outs[0].swap(w->gz_member);
@@ -852,9 +862,11 @@ void Pipeline::split_reads(Work* wp) { /* before note_reads: readBase is the ind
         if (plan[(size_t)wk].empty()) continue;
         auto job = [this, split, wp, wk, fl, ranges = std::move(plan[(size_t)wk])]() {
             const bool notes = out.comments && wp->batch.bam_backed; /* --comment_tags: the comments go into formatted text */
-            const bool gather = !fl && !split->gzipped() && !notes;
+            const bool fix = out.reindexComments && !wp->batch.bam_backed; /* --reindex_comments: the same */
+            const bool gather = !fl && !split->gzipped() && !notes && !fix;
             vector<struct iovec> iov;
             vector<fplh::BamTagSrc> src;
+            vector<fplh::FqCommentSrc> fixSrc;
             string text;
             for (const PackRange& r : ranges) {
                 if (gather) { /* the worker's getWriter1()->writeString(outstr), as a gather list over the batch's arrays */
@@ -869,6 +881,13 @@ void Pipeline::split_reads(Work* wp) { /* before note_reads: readBase is the ind
                         fplh::bam_tag_sources(wp->batch, wp->res.data(), r.first, r.last, fl, false, src, true);
                         fplh::add_tag_comments(text, src.data(), src.size(), *out.comments, st);
                         for (int k = 0; k < 4; k++) g_bamCommentStats[k] += st[k];
+                    }
+                    if (fix) {
+                        uint64_t st[5] = {0, 0, 0, 0, 0};
+                        fixSrc.clear();
+                        fplh::fq_comment_sources(wp->batch, wp->res.data(), r.first, r.last, fl, false, fixSrc);
+                        fplh::reindex_comments(text, fixSrc.data(), fixSrc.size(), st);
+                        for (int k = 0; k < 5; k++) g_fqCommentStats[k] += st[k];
                     }
                     split->write(wk, text);
                 }

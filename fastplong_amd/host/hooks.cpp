@@ -15,7 +15,9 @@
 #include "bam_tags.h"
 #include "../csrc/bam_out_rules.h"
 #include "../csrc/bam_tag_rules.h"
+#include "../csrc/fq_comment_rules.h"
 #include "fastq.h"
+#include "fq_comments.h"
 #include "gzip.h"
 #include "pool.h"
 
@@ -380,6 +382,48 @@ int fplh_bam_comment_text(const uint8_t* p, uint64_t len, const char* tags, int 
 int fplh_comment_tag_list(const char* list) {
     fplh::BamCommentSelection sel;
     return fplh::parse_comment_tags(list ? list : "", sel) ? sel.n : -2;
+}
+/* test hooks of --reindex_comments.  _form: the host form as the CLI runs it on a batch read from FASTQ text (fplh_batch_read): formatted
+   in `threads` pieces, the sources derived (fq_comment_sources), the name lines rewritten (pieces_reindex_comments); n_frags != ~0u: the
+   fragment list of a --break / --mask run.  out / failed: the text of --out / --failed_out; stats: five counts each.  _line: the
+   rule's line for one output read (fpl::fqcomment::line_text) and its five counts */
+int fplh_fq_comment_form(void* bv, const fpl_read_result* res, const fpl_fragment* frags, uint32_t n_frags, const fpl_region* regs, uint32_t n_regs,
+                         int threads, char** out, uint64_t* out_len, char** failed, uint64_t* failed_len, uint64_t* stats) {
+    const Batch& b = *(Batch*)bv;
+    fplh::FragmentList fl;
+    const bool fragments = n_frags != ~0u;
+    if (fragments) {
+        fl.frags.assign(frags, frags + n_frags);
+        fl.regs.assign(regs, regs + n_regs);
+        fl.index(b.n());
+    }
+    std::vector<std::string> o, f;
+    fplh::format_batch_parallel(b, res, threads, o, &f, fragments ? &fl : nullptr);
+    std::vector<fplh::FqCommentSrc> so, sf;
+    fplh::fq_comment_sources(b, res, 0, b.n(), fragments ? &fl : nullptr, false, so);
+    fplh::fq_comment_sources(b, res, 0, b.n(), fragments ? &fl : nullptr, true, sf);
+    for (int k = 0; k < 10; k++) stats[k] = 0;
+    fplh::pieces_reindex_comments(o, so, stats);
+    fplh::pieces_reindex_comments(f, sf, stats + 5);
+    std::string oo, ff;
+    for (auto& x : o) oo += x;
+    for (auto& x : f) ff += x;
+    hand_out(oo, out, out_len);
+    hand_out(ff, failed, failed_len);
+    return 0;
+}
+int fplh_fq_comment_line(const uint8_t* fmt, uint64_t fmt_len, const uint8_t* line, uint64_t len, const uint8_t* bases, uint64_t l_seq, uint64_t s,
+                         uint64_t n, int changed, int failed, int fragment_mode, char** out, uint64_t* out_len, uint64_t* counts) {
+    struct Sink {
+        std::string s;
+        void put(const char* q, uint32_t k) { s.append(q, k); }
+        void copy(const uint8_t* q, uint64_t k) { s.append((const char*)q, (size_t)k); }
+    } sink;
+    fpl::fqcomment::Counts c = {0, 0, 0, 0, 0};
+    fpl::fqcomment::line_text(fmt, fmt_len, line, len, bases, l_seq, s, n, changed != 0, failed != 0, fragment_mode != 0, sink, c);
+    counts[0] = c.reindexed, counts[1] = c.lost, counts[2] = c.kept, counts[3] = c.cut, counts[4] = c.left;
+    hand_out(sink.s, out, out_len);
+    return 0;
 }
 int fplh_have_libdeflate(void) { return fplh::have_libdeflate() ? 1 : 0; }
 /* the single-member lane's inflater (fplh::set_gzip_inflater) and its counts */
